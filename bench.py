@@ -3,11 +3,17 @@
 (UNetWithBackbone resnet34, no attention, batch 16 per GPU), BASELINE.json
 configs[1] (N=1) / configs[2] (N>1, weak scaling, 16 per rank).
 
-python bench.py --gpus N --steps K --warmup W
+python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 N>1: one process per GPU.  Under torch.distributed.run (WORLD_SIZE set) every
 rank runs the step; started bare, the parent launches
 `python -m torch.distributed.run --nproc-per-node N` itself (before any GPU
 call) and exits with its return code.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line.
+--full adds everything that takes runs of its own: the step-0 mIoU parity leg
+against the CPU oracle, the per-launch roofline step and the timed CPU
+baseline.  --dump-outputs DIR writes what the last timed step returned
+(logits and loss) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -105,6 +111,25 @@ def cpu_baseline_data(frames, masks, size: int, n: int):
             "sample": f"{n} frames through oracle/dataset_ref.py (numpy, one thread)"}
 
 
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: all files of one run (every rank) together
+
+
+def dump_outputs(out_dir: str, arrays: dict, rank: int = 0, world: int = 1):
+    """--dump-outputs: write each output tensor as out_dir/<name>.npy
+    (<name>.rank<r>.npy when world > 1) in float32 (float64 stays float64).
+    An array over its share of the 64 MB budget is written as a fixed sample:
+    the elements at sorted flat indices drawn from default_rng(0), the same
+    indices for every run of the same shape."""
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_BUDGET_BYTES // (world * len(arrays)) - 1024  # 1 KiB per file for the .npy header
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+        if a.nbytes > cap:
+            idx = np.sort(np.random.default_rng(0).integers(0, a.size, cap // a.itemsize))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy" if world == 1 else f"{name}.rank{rank}.npy"), a)
+
+
 def data_bench(args):
     """--data: throughput of the on-GPU data pipeline (SURVEY.md §8(f) row 3,
     dataset.py:30-66,147-151) on decoded uint8 frames resident in HBM: resize
@@ -124,7 +149,7 @@ def data_bench(args):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        pkg.preprocess(x, m, (args.size, args.size))
+        pre = pkg.preprocess(x, m, (args.size, args.size))
     torch.cuda.synchronize()
     dt_pre = (time.perf_counter() - t0) / args.steps
     t0 = time.perf_counter()
@@ -135,10 +160,13 @@ def data_bench(args):
     line = {"metric": f"preprocessed frames/sec (uint8 {src}x{src} -> float32 {args.size}x{args.size}, "
                       "clip+CLAHE+min-max+mask)",
             "value": round(n / dt_pre, 1), "unit": "frames/sec", "n_gpus": 1, "steps": args.steps,
-            "warmup": args.warmup, "higher_is_better": True, "data": "synthetic uint8 frames",
+            "warmup": args.warmup, "ms_per_step": round(dt_pre * 1e3, 3), "higher_is_better": True,
+            "dtype": "uint8 -> float32", "data": "synthetic uint8 frames",
             "config": {"workload": "dataset.py preprocessing on GPU", "batch": n},
             "augment_frames_per_sec": round(n / dt_aug, 1)}
-    if not args.no_cpu_baseline:
+    if args.dump_outputs:  # the last timed preprocessing step's (images, masks)
+        dump_outputs(args.dump_outputs, {"images": pre[0], "masks": pre[1]})
+    if args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline_data(frames, masks, args.size, args.cpu_frames)
     print(json.dumps(line), flush=True)
 
@@ -181,6 +209,54 @@ def miou_parity(model, x, y, width: int, attention: bool, backbone: str = "resne
     return miou, miou_ref
 
 
+def roofline_leg(args, model, eager_step, step_seconds: float):
+    """--full: the result line's `roofline` object.  Dominant kernel family
+    (implicit-GEMM conv fwd/dgrad/wgrad): per-launch HIP events around every
+    launch of one eager step right after the timed region."""
+    flops_step = model.step_flops((args.batch, 1, args.size, args.size), training=True)
+    step_tflops = flops_step / step_seconds / 1e12
+    plan = model._last_plan
+    torch.cuda.synchronize()
+    plan.profile(True)
+    eager_step()
+    torch.cuda.synchronize()
+    recs = plan.profile_report()
+    plan.profile(False)
+    conv = [r for r in recs if r[2] > 0]
+    conv_ms = sum(r[1] for r in conv)
+    conv_tflops = sum(r[2] for r in conv) / 1e9 / conv_ms if conv_ms > 0 else 0.0
+    kernel_ms_total = sum(r[1] for r in recs)
+    # dominant kernel = the conv template instance with the most event time
+    by_kernel = {}
+    for name, ms_, fl, kern in conv:
+        k = by_kernel.setdefault(kern, [0.0, 0.0, 0])
+        k[0] += ms_
+        k[1] += fl
+        k[2] += 1
+    dom = max(by_kernel, key=lambda k: by_kernel[k][0])
+    dom_ms, dom_fl, dom_n = by_kernel[dom]
+    achieved_tflops = dom_fl / 1e9 / dom_ms
+    dom_peak = MFMA_FP8_PEAK_TFLOPS if dom.startswith("conv_f8_kernel") else MFMA_BF16_PEAK_TFLOPS
+    traffic, traffic_src = pmc_traffic(dom, config_key(args.backbone, args.width, args.attention, args.fp8,
+                                                        args.batch, args.size))
+    dom_us = dom_ms / dom_n * 1e3
+    return {"bound": "mfma", "achieved": round(achieved_tflops, 2), "peak": dom_peak,
+            "unit": "TFLOP/s", "frac": round(achieved_tflops / dom_peak, 4),
+            "traffic": traffic,
+            # PMC bytes per launch (committed profile named here) over this
+            # run's measured average launch time: the kernel's HBM rate
+            "traffic_source": traffic_src,
+            "hbm_gbs": None if traffic is None else round(traffic / dom_us / 1e3, 1),
+            "hbm_peak_gbs": HBM_PEAK_GBS,
+            "kernel": dom, "launches_per_step": dom_n,
+            "avg_launch_us": round(dom_us, 2),
+            "kernel_ms_per_step": round(dom_ms, 3),
+            "conv_family_tflops": round(conv_tflops, 2), "conv_ms_per_step": round(conv_ms, 3),
+            "all_kernels_ms_per_step": round(kernel_ms_total, 3),
+            "step_tflops": round(step_tflops, 2),
+            "step_frac": round(step_tflops / MFMA_BF16_PEAK_TFLOPS, 4)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -202,8 +278,14 @@ def main():
                     help="forward convs with >= 128 input channels in fp8 e4m3 (configs[4] Wide fp8); bwd bf16")
     ap.add_argument("--cpu-steps", type=int, default=2)
     ap.add_argument("--cpu-threads", type=int, default=int(os.environ.get("OMP_NUM_THREADS", "16")))
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the timed CPU oracle baseline")
-    ap.add_argument("--no-parity", action="store_true", help="skip the step-0 mIoU parity leg against the CPU oracle")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the step-0 mIoU parity leg against the CPU oracle, the per-launch roofline step "
+                         "and the timed CPU baseline (each takes a run of its own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (logits, loss) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the timed CPU oracle baseline")
+    ap.add_argument("--no-parity", action="store_true",
+                    help="--full: skip the step-0 mIoU parity leg against the CPU oracle")
     ap.add_argument("--graph", dest="graph", action="store_true", default=None,
                     help="replay the step as one HIP graph (default for --gpus 1)")
     ap.add_argument("--no-graph", dest="graph", action="store_false")
@@ -246,7 +328,7 @@ def main():
     y = torch.from_numpy(ms).to(dev)
     model.train()
     parity = None
-    if not args.no_parity:  # step-0 weights; the HIP forward on every rank, the oracle on rank 0
+    if args.full and not args.no_parity:  # step-0 weights; the HIP forward on every rank, the oracle on rank 0
         parity = miou_parity(model, x, y, args.width, args.attention, args.backbone, reference=rank == 0)
         if rank != 0:
             parity = None
@@ -283,37 +365,10 @@ def main():
         dt = float(t.item())
     # metric side: mIoU (reference aggregation) of the last step's pre-step logits
     miou = pkg.calculate_metrics_from_logits(out.detach(), y)["iou"]
+    if args.dump_outputs:  # before the roofline leg's eager step touches the plan's buffers
+        dump_outputs(args.dump_outputs, {"logits": out, "loss": loss}, rank, world)
     imgs = args.batch * args.steps * world
-    flops_step = model.step_flops((args.batch, 1, args.size, args.size), training=True)
     ms_step = dt / args.steps * 1e3
-    step_tflops = flops_step / (dt / args.steps) / 1e12
-    # dominant kernel family (implicit-GEMM conv fwd/dgrad/wgrad): per-launch HIP
-    # events around every launch of one eager step right after the timed region
-    plan = model._last_plan
-    torch.cuda.synchronize()
-    plan.profile(True)
-    eager_step()
-    torch.cuda.synchronize()
-    recs = plan.profile_report()
-    plan.profile(False)
-    conv = [r for r in recs if r[2] > 0]
-    conv_ms = sum(r[1] for r in conv)
-    conv_tflops = sum(r[2] for r in conv) / 1e9 / conv_ms if conv_ms > 0 else 0.0
-    kernel_ms_total = sum(r[1] for r in recs)
-    # dominant kernel = the conv template instance with the most event time
-    by_kernel = {}
-    for name, ms_, fl, kern in conv:
-        k = by_kernel.setdefault(kern, [0.0, 0.0, 0])
-        k[0] += ms_
-        k[1] += fl
-        k[2] += 1
-    dom = max(by_kernel, key=lambda k: by_kernel[k][0])
-    dom_ms, dom_fl, dom_n = by_kernel[dom]
-    achieved_tflops = dom_fl / 1e9 / dom_ms
-    dom_peak = MFMA_FP8_PEAK_TFLOPS if dom.startswith("conv_f8_kernel") else MFMA_BF16_PEAK_TFLOPS
-    traffic, traffic_src = pmc_traffic(dom, config_key(args.backbone, args.width, args.attention, args.fp8,
-                                                        args.batch, args.size))
-    dom_us = dom_ms / dom_n * 1e3
     line = {
         "metric": "images/sec + mIoU, 512x512 U-Net bf16 at 1/2/4/8 MI355X",
         "value": round(imgs / dt, 3),
@@ -337,25 +392,11 @@ def main():
                    "global_batch": args.batch * world, "image": f"{args.size}x{args.size}",
                    "parallelism": f"dp{world}", "fp8": bool(args.fp8),
                    "grad_exchange": args.grad_dtype if world > 1 else None},
-        "roofline": {"bound": "mfma", "achieved": round(achieved_tflops, 2), "peak": dom_peak,
-                     "unit": "TFLOP/s", "frac": round(achieved_tflops / dom_peak, 4),
-                     "traffic": traffic,
-                     # PMC bytes per launch (committed profile named here) over this
-                     # run's measured average launch time: the kernel's HBM rate
-                     "traffic_source": traffic_src,
-                     "hbm_gbs": None if traffic is None else round(traffic / dom_us / 1e3, 1),
-                     "hbm_peak_gbs": HBM_PEAK_GBS,
-                     "kernel": dom, "launches_per_step": dom_n,
-                     "avg_launch_us": round(dom_us, 2),
-                     "kernel_ms_per_step": round(dom_ms, 3),
-                     "conv_family_tflops": round(conv_tflops, 2), "conv_ms_per_step": round(conv_ms, 3),
-                     "all_kernels_ms_per_step": round(kernel_ms_total, 3),
-                     "step_tflops": round(step_tflops, 2),
-                     "step_frac": round(step_tflops / MFMA_BF16_PEAK_TFLOPS, 4)},
+        "roofline": roofline_leg(args, model, eager_step, dt / args.steps) if args.full else None,
         "graph": bool(use_graph),
         "optimizer": "torch.optim.Adam (foreach)" if args.torch_adam else "fused HIP Adam (unet_adam_step)",
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(args.batch, args.size, args.cpu_steps, args.cpu_threads, args.width,
                                             args.attention, args.backbone)
     if rank == 0:
