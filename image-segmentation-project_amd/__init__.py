@@ -10,7 +10,7 @@ computed by hand-written gfx950 HIP kernels in ``libunet_hip.so`` (C ABI:
 from .advanced_models import UNetWithBackbone  # noqa: F401
 from .losses import BCELoss, ComboLoss, DiceLoss, get_loss_function  # noqa: F401
 from .utils import (EarlyStopping, calculate_metrics, calculate_metrics_from_logits,  # noqa: F401
-                    get_device)
+                    calculate_metrics_per_class, calculate_metrics_per_class_from_logits, get_device)
 from .train import (evaluate, quick_train, train_epoch, train_model, TensorLoader,  # noqa: F401
                     GraphedTrainStep)
 from .synthetic import random_batch, synthetic_cells  # noqa: F401

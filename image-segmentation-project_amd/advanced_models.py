@@ -184,11 +184,15 @@ class _UNetFunction(torch.autograd.Function):
         ctx.model = model
         ctx.plan = plan
         ctx.generation = plan.generation
+        ctx.logits_shape = tuple(logits.shape)
         ctx.save_for_backward(x)
         return logits
 
     @staticmethod
     def backward(ctx, grad_logits):
+        if tuple(grad_logits.shape) != ctx.logits_shape:
+            raise ValueError(f"grad_logits has shape {tuple(grad_logits.shape)}, the logits have "
+                             f"{ctx.logits_shape}")
         (x,) = ctx.saved_tensors
         model, plan = ctx.model, ctx.plan
         if plan.generation != ctx.generation:
@@ -213,6 +217,8 @@ class UNetWithBackbone(nn.Module):
     without attention): forward convs with >= 128 input channels run on the
     fp8 e4m3 block-scaled MFMA with per-tensor delayed scaling; BN, the loss
     and the whole backward stay bf16/fp32.
+    ``n_classes`` = 1..16 independent sigmoid channels: logits and targets are
+    ``[N, n_classes, H, W]``; the losses and metrics apply element-wise.
     """
 
     def __init__(self, n_classes=1, backbone="resnet34", pretrained=True, use_attention=True, width=1, fp8=False):
@@ -225,8 +231,10 @@ class UNetWithBackbone(nn.Module):
                                       "(densenet121 is broken in the reference, SURVEY.md §2 row 1)")
         if backbone == "resnet50" and width != 1:
             raise NotImplementedError("width != 1 is a resnet34 build extension")
-        if n_classes != 1:
-            raise NotImplementedError("n_classes must be 1 (binary segmentation, advanced_models.py:160)")
+        if not isinstance(n_classes, int) or not 1 <= n_classes <= 16:
+            raise NotImplementedError(f"n_classes={n_classes!r}: the native head is built for 1..16 sigmoid "
+                                      "channels (conv_final, advanced_models.py:160)")
+        self.n_classes = n_classes
         if pretrained:
             warnings.warn("pretrained=True needs ImageNet weights from the network (unavailable offline); "
                           "the encoder keeps its random init — load a state_dict instead", RuntimeWarning)
@@ -297,7 +305,8 @@ class UNetWithBackbone(nn.Module):
         key = (n, h, w, x.device)
         plan = self._plans.get(key)
         if plan is None:
-            plan = _Plan(n, h, w, self.width, 1, x.device, self.use_attention, self._backbone_id, self.fp8)
+            plan = _Plan(n, h, w, self.width, self.n_classes, x.device, self.use_attention, self._backbone_id,
+                         self.fp8)
             names = [k for k, _ in self.named_parameters()]
             if names != plan.param_names:
                 raise RuntimeError("native parameter table does not match the module's named_parameters()")
@@ -330,7 +339,7 @@ class UNetWithBackbone(nn.Module):
         _lib.require_gpu(x)
         x = x.contiguous().float()
         n, _, h, w = x.shape
-        logits = torch.empty((n, 1, h, w), dtype=torch.float32, device=x.device)
+        logits = torch.empty((n, self.n_classes, h, w), dtype=torch.float32, device=x.device)
         pa, ba = self._pointer_arrays()
         plan.generation += 1
         rc = plan.lib.unet_forward(plan.handle, x.data_ptr(), pa, ba, plan.workspace.data_ptr(), logits.data_ptr(),
@@ -365,8 +374,8 @@ class UNetWithBackbone(nn.Module):
         """Algorithmic FLOPs of one step at input shape [N,1,H,W]."""
         n, _, h, w = x_shape
         lib = _lib.load()
-        cfg = _lib.UnetConfig(n, h, w, self.width, 1, 1e-5, 0.1, 1 if self.use_attention else 0, self._backbone_id,
-                              1 if self.fp8 else 0)
+        cfg = _lib.UnetConfig(n, h, w, self.width, self.n_classes, 1e-5, 0.1, 1 if self.use_attention else 0,
+                              self._backbone_id, 1 if self.fp8 else 0)
         handle = ctypes.c_void_p()
         _lib.check(lib.unet_plan_create(ctypes.byref(cfg), ctypes.byref(handle)), "unet_plan_create")
         try:

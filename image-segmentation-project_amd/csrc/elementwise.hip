@@ -1015,15 +1015,457 @@ __global__ void __launch_bounds__(256) head_grads_kernel(HeadArgs a) {
   if (threadIdx.x == 0) a.gbf[0] = (float)S;
 }
 
+// ---------------------------------------------------------------------------
+// K-class head (2 <= K <= kHeadMaxClasses): conv_final has K output channels,
+// the logits are K NCHW planes.  V[k][c][ab] and cst[k] sit in LDS (K padded to
+// the class chunk with zero rows); K == 1 keeps the kernels above.
+//
+// Forward: a thread holds kHeadFwdHP pixels' activations (packed bf16, the
+// folded BN + ReLU already applied) and walks the classes kHeadFwdKC at a time;
+// one broadcast LDS read of V[k][c][0..3] feeds kHeadFwdHP pixels' FMAs, so the
+// LDS return path carries a quarter of what a read per pixel would.
+//
+// Backward: U[k][c][ab] for every class does not fit a thread's registers
+// (K * 32 per thread), and U together with dX leaves one wave per SIMD, which
+// hides no memory latency.  So the backward is ceil(K / kHeadBwdKC) + 1
+// launches over the same pixels: a U pass per chunk of kHeadBwdKC classes
+// (x and that chunk's dl re-read), then one dX pass over all K classes with
+// the ReLU mask and the fused BN-backward sums.  Partials are reduced over a
+// wave's pixel rows with shuffles, over the 4 waves through a small LDS array,
+// then added to the fp64 replicas usum[rep][k][Cin*4 + 1].
+// ---------------------------------------------------------------------------
+constexpr int kHeadFwdKC = 2;
+constexpr int kHeadFwdHP = 4;  // pixels in flight per thread (one V read feeds all of them)
+constexpr int kHeadBwdKC = 4;
+constexpr int kHeadBwdHP = 2;  // pixels in flight per thread (U[4][8][4] is 128 registers)
+static_assert(kHeadMaxClasses % kHeadFwdKC == 0 && kHeadMaxClasses % kHeadBwdKC == 0, "V is padded to the chunk");
+
+// V [Kpad][Cin*4], cst [Kpad]; rows K..Kpad-1 are zero.  Same o-order as head_contract.
+__device__ void head_contract_mc(const HeadArgs& a, float* V, float* cst, int Kpad) {
+  const int per = a.Cin * 4;
+  for (int t = threadIdx.x; t < Kpad * per; t += blockDim.x) {
+    const int k = t / per, r = t - k * per, c = r >> 2, ab = r & 3;
+    float v = 0.f;
+    if (k < a.K)
+      for (int o = 0; o < a.Co; ++o) v += a.wf[k * a.Co + o] * a.w0[((size_t)c * a.Co + o) * 4 + ab];
+    V[t] = v;
+  }
+  for (int k = threadIdx.x; k < Kpad; k += blockDim.x) {
+    float c0 = 0.f;
+    if (k < a.K) {
+      c0 = a.bf[k];
+      for (int o = 0; o < a.Co; ++o) c0 += a.wf[k * a.Co + o] * a.b0[o];
+    }
+    cst[k] = c0;
+  }
+  __syncthreads();
+}
+
+template <int CIN>
+__global__ void __launch_bounds__(256) head_fwd_mc_kernel(HeadArgs a) {
+  constexpr int KC = kHeadFwdKC;
+  __shared__ __attribute__((aligned(16))) float V[kHeadMaxClasses * CIN * 4];
+  __shared__ __attribute__((aligned(8))) float2 bss[kHeadMaxCin];
+  __shared__ float cst[kHeadMaxClasses];
+  const bool fold = a.bn_fold != 0;
+  const int K = a.K;
+  if (fold) head_bn_coef(a, bss);  // (head_contract_mc's barrier publishes it)
+  head_contract_mc(a, V, cst, (K + KC - 1) / KC * KC);
+  constexpr int CC = CIN / 8;
+  const int total = a.N * a.H * a.W, HW = a.H * a.W, W2 = 2 * a.W;
+  const int plane = 4 * HW;  // one class's logits of one image
+  const int stride = gridDim.x * blockDim.x;
+  for (int p0 = blockIdx.x * blockDim.x + threadIdx.x; p0 < total; p0 += kHeadFwdHP * stride) {
+    uint4 xv[kHeadFwdHP][CC];
+    int obase[kHeadFwdHP];  // class 0's logits of the pixel (32-bit: the launcher bounds N*K*4*H*W)
+#pragma unroll
+    for (int u = 0; u < kHeadFwdHP; ++u) {
+      const int pix = p0 + u * stride;
+      const bool ok = pix < total;
+#pragma unroll
+      for (int q = 0; q < CC; ++q)
+        xv[u][q] = ok ? *reinterpret_cast<const uint4*>(a.x + (size_t)pix * a.ldx + q * 8) : make_uint4(0, 0, 0, 0);
+      const int pc = ok ? pix : 0;
+      const int n = pc / HW, r = pc - n * HW, i = r / a.W, j = r - i * a.W;
+      obase[u] = ok ? (n * K * 2 * a.H + 2 * i) * W2 + 2 * j : -1;
+    }
+    if (fold) {  // act = bf16(relu(bn(y))), kept packed: every class chunk unpacks the same bits
+#pragma unroll
+      for (int u = 0; u < kHeadFwdHP; ++u)
+#pragma unroll
+        for (int q = 0; q < CC; ++q) {
+          float x[8];
+          unpack8(xv[u][q], x);
+#pragma unroll
+          for (int k = 0; k < 8; ++k) {
+            const float2 s = bss[q * 8 + k];
+            x[k] = head_act(x[k], s.x, s.y);
+          }
+          xv[u][q] = pack8(x);
+        }
+    }
+    for (int k0 = 0; k0 < K; k0 += KC) {
+      // opaque per chunk: the unpacked activations (kHeadFwdHP * CIN floats) are
+      // re-formed here, not hoisted out of the class loop into registers
+#pragma unroll
+      for (int u = 0; u < kHeadFwdHP; ++u)
+#pragma unroll
+        for (int q = 0; q < CC; ++q)
+          asm volatile("" : "+v"(xv[u][q].x), "+v"(xv[u][q].y), "+v"(xv[u][q].z), "+v"(xv[u][q].w));
+      float o[kHeadFwdHP][KC][4];
+#pragma unroll
+      for (int kk = 0; kk < KC; ++kk) {
+        const float c0 = cst[k0 + kk];
+#pragma unroll
+        for (int u = 0; u < kHeadFwdHP; ++u) o[u][kk][0] = o[u][kk][1] = o[u][kk][2] = o[u][kk][3] = c0;
+      }
+#pragma unroll
+      for (int q = 0; q < CC; ++q) {
+        float x[kHeadFwdHP][8];
+#pragma unroll
+        for (int u = 0; u < kHeadFwdHP; ++u) unpack8(xv[u][q], x[u]);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          // at most 4 channels' V reads in flight (the scheduler would otherwise
+          // issue the whole chunk's LDS reads first: CIN * KC * 4 registers)
+          if ((k & 3) == 0) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int kk = 0; kk < KC; ++kk) {  // a broadcast read shared by the kHeadFwdHP pixels
+            const float4 v = *reinterpret_cast<const float4*>(V + ((k0 + kk) * CIN + q * 8 + k) * 4);
+#pragma unroll
+            for (int u = 0; u < kHeadFwdHP; ++u) {
+              o[u][kk][0] += x[u][k] * v.x; o[u][kk][1] += x[u][k] * v.y;
+              o[u][kk][2] += x[u][k] * v.z; o[u][kk][3] += x[u][k] * v.w;
+            }
+          }
+        }
+      }
+      // the sums are formed here, in channel order, for every pixel slot: without
+      // this the FMAs sink into the per-pixel store branches below and every V
+      // read of the chunk is issued (and held in registers) ahead of them
+#pragma unroll
+      for (int u = 0; u < kHeadFwdHP; ++u)
+#pragma unroll
+        for (int kk = 0; kk < KC; ++kk)
+          asm volatile("" : "+v"(o[u][kk][0]), "+v"(o[u][kk][1]), "+v"(o[u][kk][2]), "+v"(o[u][kk][3]));
+#pragma unroll
+      for (int u = 0; u < kHeadFwdHP; ++u) {
+        if (obase[u] < 0) continue;
+#pragma unroll
+        for (int kk = 0; kk < KC; ++kk) {
+          if (k0 + kk >= K) break;
+          float* row0 = a.logits + (size_t)(obase[u] + (k0 + kk) * plane);
+          *reinterpret_cast<float2*>(row0) = make_float2(o[u][kk][0], o[u][kk][1]);
+          *reinterpret_cast<float2*>(row0 + W2) = make_float2(o[u][kk][2], o[u][kk][3]);
+        }
+      }
+    }
+  }
+  if (fold && blockIdx.x == 0 && !a.bn.ss) bn_finalize_block0(a.bn, threadIdx.x, blockDim.x, 0, a.Cin);
+}
+
+// sum over the lanes that hold the same 8-channel chunk (lane % CC) of a wave
+template <int CC>
+__device__ __forceinline__ float head_rows_sum(float v) {
+#pragma unroll
+  for (int m = CC; m < 64; m <<= 1) v += __shfl_xor(v, m);
+  return v;
+}
+
+// dl of kHeadBwdKC classes (from kc0) at the thread's kHeadBwdHP pixels; zero
+// past K and past the last pixel
+__device__ __forceinline__ void head_load_dl(const float* dl, const int* dbase, int kc0, int K, int plane, int W2,
+                                             float (&d)[kHeadBwdKC][kHeadBwdHP][4]) {
+#pragma unroll
+  for (int kk = 0; kk < kHeadBwdKC; ++kk)
+#pragma unroll
+    for (int u = 0; u < kHeadBwdHP; ++u) {
+      float2 d01 = make_float2(0.f, 0.f), d23 = d01;
+      if (dbase[u] >= 0 && kc0 + kk < K) {
+        const float* row0 = dl + (size_t)(dbase[u] + (kc0 + kk) * plane);
+        d01 = *reinterpret_cast<const float2*>(row0);
+        d23 = *reinterpret_cast<const float2*>(row0 + W2);
+      }
+      d[kk][u][0] = d01.x; d[kk][u][1] = d01.y; d[kk][u][2] = d23.x; d[kk][u][3] = d23.y;
+    }
+}
+
+// Pass U: U[k][c][ab] and S[k] of the classes k0 .. k0 + kHeadBwdKC - 1 into usum.
+// thread = (8-channel chunk, pixel row), as in head_bwd_kernel.
+template <int CIN>
+__global__ void __launch_bounds__(256) head_bwd_u_mc_kernel(HeadArgs a, int k0) {
+  constexpr int KC = kHeadBwdKC, HP = kHeadBwdHP;
+  constexpr int CC = CIN / 8, rows = 256 / CC;
+  constexpr int LU = CIN * 4 + 1;  // one class: U (Cin*4) | S
+  __shared__ __attribute__((aligned(8))) float2 bss[kHeadMaxCin];
+  __shared__ float red[4][KC * LU];
+  const bool fold = a.bn_fold != 0;  // x = y: act recomputed
+  const int K = a.K;
+  if (fold) {
+    head_bn_coef(a, bss);
+    __syncthreads();
+  }
+  const int chunk = threadIdx.x % CC, row = threadIdx.x / CC;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int c8 = chunk << 3;
+  const int total = a.N * a.H * a.W, HW = a.H * a.W, W2 = 2 * a.W;
+  const int plane = 4 * HW;
+  const int stride = gridDim.x * rows;
+  float U[KC][8][4], S[KC];
+#pragma unroll
+  for (int kk = 0; kk < KC; ++kk) {
+    S[kk] = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+#pragma unroll
+      for (int ab = 0; ab < 4; ++ab) U[kk][k][ab] = 0.f;
+  }
+  for (int p0 = blockIdx.x * rows + row; p0 < total; p0 += HP * stride) {
+    uint4 xv[HP];
+    int dbase[HP];  // class 0's dlogits of the pixel, -1 past the end (32-bit: the launcher bounds N*K*4*H*W)
+#pragma unroll
+    for (int u = 0; u < HP; ++u) {
+      const int pix = p0 + u * stride;
+      const bool ok = pix < total;
+      const int pc = ok ? pix : 0;
+      const int n = pc / HW, r = pc - n * HW, i = r / a.W, j = r - i * a.W;
+      dbase[u] = ok ? (n * K * 2 * a.H + 2 * i) * W2 + 2 * j : -1;
+      xv[u] = ok ? *reinterpret_cast<const uint4*>(a.x + (size_t)pc * a.ldx + c8) : make_uint4(0, 0, 0, 0);
+    }
+    float d[KC][HP][4];
+    head_load_dl(a.dl, dbase, k0, K, plane, W2, d);
+#pragma unroll
+    for (int u = 0; u < HP; ++u) {
+      float x[8];
+      unpack8(xv[u], x);
+      if (fold) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const float2 s = bss[c8 + k];
+          x[k] = head_act(x[k], s.x, s.y);
+        }
+      }
+#pragma unroll
+      for (int kk = 0; kk < KC; ++kk) {
+        if (chunk == 0) S[kk] += (d[kk][u][0] + d[kk][u][1]) + (d[kk][u][2] + d[kk][u][3]);
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+#pragma unroll
+          for (int ab = 0; ab < 4; ++ab) U[kk][k][ab] += x[k] * d[kk][u][ab];
+      }
+    }
+  }
+  // rows of a wave by shuffles, the 4 waves through red, then the fp64 replicas
+  const int nk = K - k0 < KC ? K - k0 : KC;
+#pragma unroll
+  for (int kk = 0; kk < KC; ++kk) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+#pragma unroll
+      for (int ab = 0; ab < 4; ++ab) {
+        const float v = head_rows_sum<CC>(U[kk][k][ab]);
+        if (lane < CC) red[wave][kk * LU + (c8 + k) * 4 + ab] = v;
+      }
+    const float sv = head_rows_sum<CC>(S[kk]);
+    if (lane == 0) red[wave][kk * LU + CIN * 4] = sv;
+  }
+  __syncthreads();
+  for (int t = threadIdx.x; t < nk * LU; t += blockDim.x) {  // [kStatRep][K][Cin*4 + 1] replicas
+    const float v = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
+    atomicAdd(a.usum + ((size_t)(blockIdx.x % kStatRep) * K + k0) * LU + t, (double)v);
+  }
+}
+
+// Pass dX: dX[c] = sum_k sum_ab dl[k][ab] V[k][c][ab], then (bb.sums != null)
+// the ReLU mask and the fused BN-backward sums, as head_bwd_kernel.
+template <int CIN>
+__global__ void __launch_bounds__(256) head_bwd_dx_mc_kernel(HeadArgs a) {
+  constexpr int KC = kHeadBwdKC, HP = kHeadBwdHP;
+  constexpr int CC = CIN / 8, rows = 256 / CC;
+  __shared__ __attribute__((aligned(16))) float V[kHeadMaxClasses * CIN * 4];
+  __shared__ __attribute__((aligned(8))) float2 bss[kHeadMaxCin];
+  __shared__ __attribute__((aligned(8))) float2 mis[kHeadMaxCin];  // the fused BN's mean, invstd
+  __shared__ float cst[kHeadMaxClasses];
+  __shared__ float red[4][2 * CIN];
+  const bool fold = a.bn_fold != 0;  // x = y: act recomputed (the launcher checks bb.y == x)
+  const BnBwdArgs& bb = a.bb;
+  const bool fz = bb.sums != nullptr;
+  const int K = a.K;
+  if (fold) head_bn_coef(a, bss);
+  if (fz)
+    for (int c = threadIdx.x; c < CIN; c += blockDim.x) mis[c] = make_float2(bb.mean[c], bb.invstd[c]);
+  head_contract_mc(a, V, cst, (K + KC - 1) / KC * KC);
+  const int chunk = threadIdx.x % CC, row = threadIdx.x / CC;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int c8 = chunk << 3;
+  const int total = a.N * a.H * a.W, HW = a.H * a.W, W2 = 2 * a.W;
+  const int plane = 4 * HW;
+  const int stride = gridDim.x * rows;
+  float s1[8], s2[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) s1[k] = s2[k] = 0.f;
+  for (int p0 = blockIdx.x * rows + row; p0 < total; p0 += HP * stride) {
+    uint4 xv[HP], yv[HP];
+    int dbase[HP];
+#pragma unroll
+    for (int u = 0; u < HP; ++u) {
+      const int pix = p0 + u * stride;
+      const bool ok = pix < total;
+      const int pc = ok ? pix : 0;
+      const int n = pc / HW, r = pc - n * HW, i = r / a.W, j = r - i * a.W;
+      dbase[u] = ok ? (n * K * 2 * a.H + 2 * i) * W2 + 2 * j : -1;
+      // x only feeds the ReLU mask here
+      xv[u] = (ok && fz) ? *reinterpret_cast<const uint4*>(a.x + (size_t)pc * a.ldx + c8) : make_uint4(0, 0, 0, 0);
+      yv[u] = fold ? xv[u]
+                   : ((ok && fz) ? *reinterpret_cast<const uint4*>(bb.y + (size_t)pc * bb.ldy + c8)
+                                 : make_uint4(0, 0, 0, 0));
+    }
+    float g[HP][8];
+#pragma unroll
+    for (int u = 0; u < HP; ++u)
+#pragma unroll
+      for (int k = 0; k < 8; ++k) g[u][k] = 0.f;
+    for (int kc0 = 0; kc0 < K; kc0 += KC) {
+      float d[KC][HP][4];
+      head_load_dl(a.dl, dbase, kc0, K, plane, W2, d);
+#pragma unroll
+      for (int kk = 0; kk < KC; ++kk)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const float4 v = *reinterpret_cast<const float4*>(V + ((kc0 + kk) * CIN + c8 + k) * 4);
+#pragma unroll
+          for (int u = 0; u < HP; ++u)
+            g[u][k] += d[kk][u][0] * v.x + d[kk][u][1] * v.y + d[kk][u][2] * v.z + d[kk][u][3] * v.w;
+        }
+    }
+    // formed here for every pixel slot (not sunk into the store branches below)
+#pragma unroll
+    for (int u = 0; u < HP; ++u)
+      asm volatile("" : "+v"(g[u][0]), "+v"(g[u][1]), "+v"(g[u][2]), "+v"(g[u][3]), "+v"(g[u][4]), "+v"(g[u][5]),
+                   "+v"(g[u][6]), "+v"(g[u][7]));
+#pragma unroll
+    for (int u = 0; u < HP; ++u) {
+      if (dbase[u] < 0) continue;
+      const int pix = p0 + u * stride;
+      if (fz) {  // x IS the BN+ReLU output (act): ReLU mask, then the BN-backward sums
+        float x[8];
+        unpack8(xv[u], x);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          if (fold) {
+            const float2 s = bss[c8 + k];
+            x[k] = head_act(x[k], s.x, s.y);
+          }
+          g[u][k] = x[k] > 0.f ? g[u][k] : 0.f;
+        }
+      }
+      const uint4 o = pack8(g[u]);
+      *reinterpret_cast<uint4*>(a.dx + (size_t)pix * a.lddx + c8) = o;
+      if (fz) {
+        float dz[8], y[8];
+        unpack8(o, dz);  // sums of the stored bf16 dZ, as bn_bwd_reduce_kernel would read them
+        unpack8(yv[u], y);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const float2 m = mis[c8 + k];
+          s1[k] += dz[k];
+          s2[k] += dz[k] * (y[k] - m.x) * m.y;
+        }
+      }
+    }
+  }
+  if (fz) {  // [kStatRep][2][C] replica layout of the BN-backward sums
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const float v1 = head_rows_sum<CC>(s1[k]), v2 = head_rows_sum<CC>(s2[k]);
+      if (lane < CC) {
+        red[wave][c8 + k] = v1;
+        red[wave][CIN + c8 + k] = v2;
+      }
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < 2 * CIN; t += blockDim.x) {
+      const float v = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
+      atomicAdd(bb.sums + (size_t)(blockIdx.x % kStatRep) * 2 * CIN + t, (double)v);
+    }
+    if (bb.ticket) {
+      __shared__ int flag;
+      if (last_block_arrive(bb.ticket, gridDim.x, &flag, true)) bn_bwd_finalize(bb);
+    }
+  }
+}
+
+// K + 1 blocks; fp64, fixed order (replicas, then classes or c / ab).  Block
+// k < K: conv_final's row k (gwf[k][:], gbf[k]) from class k's sums, with w0
+// staged in LDS as in head_grads_kernel.  Block K: gw0 and gb0, which sum over
+// the classes (every class's sums and wf staged in LDS).
+constexpr int kHeadLU = kHeadMaxCin * 4 + 1;
+constexpr int kHeadGradsBuf = kHeadMaxClasses * kHeadLU + kHeadMaxClasses * 32 / 2;  // doubles: us | wf (floats)
+static_assert(kHeadGradsBuf >= kHeadLU + 7 + kHeadMaxW0 / 2, "row blocks: one class's sums | w0 (floats)");
+__global__ void __launch_bounds__(256) head_grads_mc_kernel(HeadArgs a) {
+  __shared__ double buf[kHeadGradsBuf];
+  const int K = a.K, LU = a.Cin * 4 + 1, nu = K * LU;
+  const int nw = a.Cin * a.Co * 4;
+  if ((int)blockIdx.x < K) {
+    const int k = blockIdx.x;
+    double* us = buf;
+    float* w0s = reinterpret_cast<float*>(buf + ((kHeadLU + 7) & ~7));
+    for (int t = threadIdx.x; t < LU; t += blockDim.x) {
+      double v = 0.0;
+#pragma unroll
+      for (int r = 0; r < kStatRep; ++r) v += a.usum[(size_t)r * nu + k * LU + t];
+      us[t] = v;
+    }
+    for (int t = threadIdx.x; t < nw; t += blockDim.x) w0s[t] = a.w0[t];
+    __syncthreads();
+    const double S = us[a.Cin * 4];
+    for (int o = threadIdx.x; o < a.Co; o += blockDim.x) {
+      double g = (double)a.b0[o] * S;
+      for (int c = 0; c < a.Cin; ++c)
+        for (int ab = 0; ab < 4; ++ab) g += (double)w0s[(c * a.Co + o) * 4 + ab] * us[c * 4 + ab];
+      a.gwf[k * a.Co + o] = (float)g;
+    }
+    if (threadIdx.x == 0) a.gbf[k] = (float)S;
+    return;
+  }
+  double* us = buf;
+  float* wfs = reinterpret_cast<float*>(buf + kHeadMaxClasses * kHeadLU);
+  for (int t = threadIdx.x; t < nu; t += blockDim.x) {
+    double v = 0.0;
+#pragma unroll
+    for (int r = 0; r < kStatRep; ++r) v += a.usum[(size_t)r * nu + t];
+    us[t] = v;
+  }
+  for (int t = threadIdx.x; t < K * a.Co; t += blockDim.x) wfs[t] = a.wf[t];
+  __syncthreads();
+  for (int t = threadIdx.x; t < nw; t += blockDim.x) {
+    const int ab = t & 3, o = (t >> 2) % a.Co, c = (t >> 2) / a.Co;
+    double g = 0.0;
+    for (int k = 0; k < K; ++k) g += (double)wfs[k * a.Co + o] * us[k * LU + c * 4 + ab];
+    a.gw0[t] = (float)g;
+  }
+  for (int o = threadIdx.x; o < a.Co; o += blockDim.x) {
+    double g = 0.0;
+    for (int k = 0; k < K; ++k) g += (double)wfs[k * a.Co + o] * us[k * LU + a.Cin * 4];
+    a.gb0[o] = (float)g;
+  }
+}
+
 // the head's pixel range in 32-bit indices (decoder1 output pixels, and the
-// 4x as many logits)
+// 4K x as many logits)
 static bool head_ok(const HeadArgs& a) {
-  return (a.Cin == 32 || a.Cin == 64) && (int64_t)a.N * a.H * a.W * 4 < 0x7fffffffLL;
+  return (a.Cin == 32 || a.Cin == 64) && a.K >= 1 && a.K <= kHeadMaxClasses &&
+         (int64_t)a.N * a.K * a.H * a.W * 4 < 0x7fffffffLL;
 }
 hipError_t launch_head_fwd(const HeadArgs& a, hipStream_t st) {
   if (!head_ok(a) || (a.bn_fold && (a.bn.C != a.Cin || !a.bn.stats))) return hipErrorInvalidValue;
   const int64_t total = (int64_t)a.N * a.H * a.W;
   const int grid = grid_for(total, 256 * kHeadHP * 2, 1024);
+  if (a.K > 1) {
+    if (a.Cin == 32) hipLaunchKernelGGL(head_fwd_mc_kernel<32>, dim3(grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(head_fwd_mc_kernel<64>, dim3(grid), dim3(256), 0, st, a);
+    return hipGetLastError();
+  }
   if (a.Cin == 32) hipLaunchKernelGGL(head_fwd_kernel<32>, dim3(grid), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(head_fwd_kernel<64>, dim3(grid), dim3(256), 0, st, a);
   return hipGetLastError();
@@ -1036,6 +1478,17 @@ hipError_t launch_head_bwd(const HeadArgs& a, hipStream_t st) {
   // the folded BN: act is recomputed from bb.y, which must be the head's x
   if (a.bn_fold && (!a.bb.sums || a.bb.y != a.x || a.bb.ldy != a.ldx || a.bn.C != a.Cin || !a.bn.stats))
     return hipErrorInvalidValue;
+  if (a.K > 1) {
+    // U passes first, a chunk of classes each, then dX (its last block finalises the fused BN sums)
+    const int g = grid_for(total, rows * kHeadBwdHP * 4, 512);
+    for (int k0 = 0; k0 < a.K; k0 += kHeadBwdKC) {
+      if (a.Cin == 32) hipLaunchKernelGGL(head_bwd_u_mc_kernel<32>, dim3(g), dim3(256), 0, st, a, k0);
+      else hipLaunchKernelGGL(head_bwd_u_mc_kernel<64>, dim3(g), dim3(256), 0, st, a, k0);
+    }
+    if (a.Cin == 32) hipLaunchKernelGGL(head_bwd_dx_mc_kernel<32>, dim3(g), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(head_bwd_dx_mc_kernel<64>, dim3(g), dim3(256), 0, st, a);
+    return hipGetLastError();
+  }
   const size_t lds = (size_t)rows * (a.Cin * 4 + 1 + (a.bb.sums ? 2 * a.Cin : 0)) * sizeof(float);
   // 512 blocks: each adds Cin*4 + 1 fp64 partials (16 replicas) at its end;
   // 1024 blocks onto one copy serialised ~1k same-address atomics per word
@@ -1045,8 +1498,10 @@ hipError_t launch_head_bwd(const HeadArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 hipError_t launch_head_grads(const HeadArgs& a, hipStream_t st) {
-  if (a.Cin > kHeadMaxCin || a.Cin * a.Co * 4 > kHeadMaxW0) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(head_grads_kernel, dim3(1), dim3(256), 0, st, a);
+  if (a.Cin > kHeadMaxCin || a.Cin * a.Co * 4 > kHeadMaxW0 || a.K < 1 || a.K > kHeadMaxClasses)
+    return hipErrorInvalidValue;
+  if (a.K > 1) hipLaunchKernelGGL(head_grads_mc_kernel, dim3(a.K + 1), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(head_grads_kernel, dim3(1), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

@@ -346,7 +346,11 @@ static int build_plan(unet_plan* p) {
             "only fix the last two levels)");
     return 1;
   }
-  if (c.n_classes != 1) { set_err("unet_plan_create: only n_classes == 1 is supported"); return 1; }
+  if (c.n_classes < 1 || c.n_classes > kHeadMaxClasses) {
+    set_err("unet_plan_create: n_classes must be 1..16 (the fused head contracts upconv0 with conv_final; "
+            "above upconv0's output channels the contracted form does more work than the two convs)");
+    return 1;
+  }
   const bool r50 = c.backbone == 50;
   if (c.backbone != 0 && c.backbone != 34 && c.backbone != 50) {
     set_err("unet_plan_create: backbone must be 34 (resnet34) or 50 (resnet50)");
@@ -500,7 +504,8 @@ static int build_plan(unet_plan* p) {
   }
   for (auto& cv : p->convs)
     if (cv.kind == L_CONVT) cv.bias_acc = A.take((size_t)kStatRep * cv.Co * sizeof(double));
-  p->head_usum = A.take((size_t)kStatRep * (up0_in * 4 + 1) * sizeof(double));  // [kStatRep][Cin*4 + 1]
+  // [kStatRep][K * (Cin*4 + 1)]
+  p->head_usum = A.take((size_t)kStatRep * c.n_classes * (up0_in * 4 + 1) * sizeof(double));
   p->stem_tkt = A.take(kStemTickets * sizeof(unsigned));
   for (auto& t : p->atts) {
     t.pbs = A.take(2 * sizeof(double));
@@ -842,7 +847,7 @@ static int build_plan(unet_plan* p) {
     fw += 2 * px * t.Fi * (t.Fg + t.Fl + 1) + 2.0 * N * 2 * 2 * t.C * t.Cr;
   }
   fw += 2.0 * N * H2 * W2 * up0_in * (c0 / 4) * 4;  // upconv0
-  fw += 2.0 * N * H * W * (c0 / 4);                    // conv_final
+  fw += 2.0 * N * H * W * (c0 / 4) * c.n_classes;      // conv_final
   p->flops_fwd = fw;
   p->flops_train = 3 * fw - stem;
 
@@ -1714,6 +1719,7 @@ static int run_forward(unet_plan* p, const float* image, const float* const* prm
     h.w0 = prm[p->up0_w]; h.b0 = prm[p->up0_b]; h.wf = prm[p->fin_w]; h.bf = prm[p->fin_b];
     h.logits = logits;
     h.N = N; h.H = o.H; h.W = o.W; h.Cin = o.C; h.Co = (int)p->params[p->up0_b].numel;
+    h.K = p->cfg.n_classes;
     ProfScope ps(p, st, hfold ? "head_fwd +bn" : "head_fwd", 0);
     CK(launch_head_fwd(h, st));
   }
@@ -1774,6 +1780,7 @@ static int run_backward(unet_plan* p, const float* image, const float* dlogits, 
     h.gw0 = grads + p->params[p->up0_w].flat; h.gb0 = grads + p->params[p->up0_b].flat;
     h.gwf = grads + p->params[p->fin_w].flat; h.gbf = grads + p->params[p->fin_b].flat;
     h.N = N; h.H = o.H; h.W = o.W; h.Cin = o.C; h.Co = (int)p->params[p->up0_b].numel;
+    h.K = p->cfg.n_classes;
     if (p->fuse_bwd && !att) {  // the head produces dA of decoder1's last BN: reduce it here
       const Dec& d = p->decs[3];
       h.bb = bwd_args(x, d.bn2, d.d_out, d.out, d.y2, d.dy2, -1, nullptr, nullptr, nullptr, grads);

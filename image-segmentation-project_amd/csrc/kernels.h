@@ -365,17 +365,20 @@ size_t stem_rc_tot_bytes(int Cout);                        // a.tot followed by 
 size_t stem_rc_imsum_offset(int Cout);                     // bytes from a.tot to a.imsum
 size_t stem_rc_l2_offset(int N, int P, int Q, int Cout);   // bytes from a.part to a.l2
 
-// fused ConvTranspose2d(k2,s2, Cin->16) + Conv1x1(16->1): logits[2i+a,2j+b] =
-// c0 + sum_c X[i,j,c] V[c][a][b],  V[c][ab] = sum_o Wf[o] W0[c][o][ab].
+// fused ConvTranspose2d(k2,s2, Cin->Co) + Conv1x1(Co->K): logits[k][2i+a,2j+b] =
+// cst[k] + sum_c X[i,j,c] V[k][c][a][b],  V[k][c][ab] = sum_o Wf[k][o] W0[c][o][ab],
+// cst[k] = bf[k] + sum_o Wf[k][o] b0[o].  K == 1 runs the single-plane kernels;
+// 2 <= K <= kHeadMaxClasses the class-chunked ones (elementwise.hip).
+constexpr int kHeadMaxClasses = 16;
 struct HeadArgs {
   const bf16_t* x; int ldx;          // decoder1 output [N,H,W,Cin]
   const float* w0; const float* b0;  // upconv0 weight [Cin][Co][2][2], bias [Co]
-  const float* wf; const float* bf;  // conv_final weight [1][Co][1][1], bias [1]
-  float* logits;                     // [N,2H,2W]
-  const float* dl;                   // backward: dL/dlogits
+  const float* wf; const float* bf;  // conv_final weight [K][Co][1][1], bias [K]
+  float* logits;                     // [N,K,2H,2W]
+  const float* dl;                   // backward: dL/dlogits, [N,K,2H,2W]
   bf16_t* dx; int lddx;              // backward: dL/dX
-  double* usum;                      // backward: [kStatRep][Cin*4 + 1] sums U[c][ab], S (zeroed replicas)
-  float* gw0; float* gb0; float* gwf; float* gbf;  // param grads
+  double* usum;                      // backward: [kStatRep][K][Cin*4 + 1] sums U[k][c][ab], S[k] (zeroed replicas)
+  float* gw0; float* gb0; float* gwf; float* gbf;  // param grads (gwf [K][Co], gbf [K])
   // backward, optional (bb.sums != null): dX is dA of decoder1's last
   // BN+ReLU; as in the conv-dgrad epilogue, dZ = dA * (act > 0) is stored and
   // the BN-backward sums (dZ, dZ*xhat) are reduced here (bn_bwd apply follows)
@@ -388,6 +391,7 @@ struct HeadArgs {
   BnLaunch bn;
   int bn_fold;
   int N, H, W, Cin, Co;
+  int K;                             // classes (conv_final's output channels), 1..kHeadMaxClasses
 };
 hipError_t launch_head_fwd(const HeadArgs& a, hipStream_t st);
 hipError_t launch_head_bwd(const HeadArgs& a, hipStream_t st);

@@ -51,6 +51,28 @@ def calculate_metrics_from_logits(logits, target) -> dict:
     return metrics_from_counts(*c)
 
 
+def _per_class(values, target, from_logits: bool) -> list:
+    if values.dim() != 4 or tuple(values.shape) != tuple(target.shape):
+        raise ValueError(f"expected [N,K,H,W] values and target of one shape, got {tuple(values.shape)} "
+                         f"and {tuple(target.shape)}")
+    out = []
+    for k in range(values.shape[1]):
+        c = mask_counts(values[:, k].contiguous(), target[:, k].contiguous(), from_logits)[4:8].tolist()
+        out.append(metrics_from_counts(*c))
+    return out
+
+
+def calculate_metrics_per_class(pred, target) -> list:
+    """``calculate_metrics`` of every channel of ``[N,K,H,W]`` probabilities: a
+    list of K dicts (the same exact counts, one reduction per channel)."""
+    return _per_class(pred, target, from_logits=False)
+
+
+def calculate_metrics_per_class_from_logits(logits, target) -> list:
+    """``calculate_metrics_from_logits`` of every channel of ``[N,K,H,W]`` logits."""
+    return _per_class(logits, target, from_logits=True)
+
+
 def get_device():
     """utils.py:153-167 — the ROCm GPU when present (torch's 'cuda' device)."""
     if torch.cuda.is_available():

@@ -39,7 +39,8 @@ typedef struct unet_plan unet_plan;
 typedef struct unet_config {
   int N, H, W;       /* batch and input size (H, W multiples of 32)            */
   int width;         /* channel multiplier: 1 = resnet34 U-Net (64..512)       */
-  int n_classes;     /* must be 1 (binary segmentation, advanced_models.py:160) */
+  int n_classes;     /* 1..16: conv_final's output channels (advanced_models.py:160), */
+                     /*    independent sigmoid channels; logits are [N,n_classes,H,W]  */
   float bn_eps;      /* 1e-5  (torch.nn.BatchNorm2d default)                   */
   float bn_momentum; /* 0.1                                                    */
   int attention;     /* 1: AttentionGate + ChannelAttention decoder            */
@@ -76,10 +77,12 @@ int unet_plan_tensor_info(const unet_plan* p, int i, char* name, int namelen, in
  * state_dict parameter order); buffers[3*k+0/1/2]: running_mean/var (fp32) and
  * num_batches_tracked (int64) of BN k in named_buffers order.  A training
  * forward updates the running statistics and adds 1 to num_batches_tracked,
- * as torch.nn.BatchNorm2d.train() does. */
+ * as torch.nn.BatchNorm2d.train() does.
+ * image: [N,1,H,W] fp32; logits: [N, n_classes, H, W] fp32 (NCHW, contiguous). */
 int unet_forward(unet_plan* p, const float* image, const float* const* params, float* const* buffers,
                  void* workspace, float* logits, int training, hipStream_t stream);
-/* grads: flat fp32 [unet_plan_grad_numel], param i at unet_plan_param_offset(i).
+/* dlogits: [N, n_classes, H, W] fp32, the logits' layout.
+ * grads: flat fp32 [unet_plan_grad_numel], param i at unet_plan_param_offset(i).
  * Ordering contract: unet_backward differentiates the LAST training
  * unet_forward of the same plan and workspace (its saved activations and BN
  * statistics).  A training forward also zeroes the backward's accumulators
