@@ -28,6 +28,23 @@ class UnetConfig(ctypes.Structure):
                 ("fp8", c_int)]
 
 
+class ConvExArgs(ctypes.Structure):
+    """unet_conv_ex_args (include/unet_hip.h): one conv launch with the whole
+    epilogue; zero / null fields are off.  size is filled in here."""
+    _fields_ = ([(n, c_int) for n in (
+        "size", "mode", "chunk_major", "grid_cap", "N", "H", "W", "C", "P", "Q", "Cout", "R", "S", "stride", "pad",
+        "ldx", "ldy", "ldadd", "ldact", "ldyraw", "ldyraw2", "ldx2", "C2", "ldysplit", "csplit", "ldyds", "relu")]
+                + [("eps", c_float)]
+                + [(n, c_void_p) for n in (
+                    "x", "w", "y", "bias", "addend", "stats", "act", "yraw", "mean", "invstd", "yraw2", "mean2",
+                    "invstd2", "bsums", "bsums2", "x2", "w2", "ysplit", "gamma", "beta", "running_mean",
+                    "running_var", "wds", "yds", "stats_ds")])
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.size = ctypes.sizeof(ConvExArgs)
+
+
 # name -> (restype, argtypes); every exported symbol of include/unet_hip.h
 SIGNATURES = {
     "unet_last_error": (c_char_p, []),
@@ -70,6 +87,8 @@ SIGNATURES = {
     "unet_grad_from_bf16": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_void_p]),
     "unet_conv_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]
                       + [c_int] * 12 + [c_void_p]),
+    "unet_conv_ex": (c_int, [ctypes.POINTER(ConvExArgs), c_void_p]),
+    "unet_last_kernel_tag": (c_char_p, []),
     "unet_conv_wgrad": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p] + [c_int] * 12 + [c_void_p]),
     "unet_conv3x3_fl": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                 c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,

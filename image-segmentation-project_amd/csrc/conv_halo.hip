@@ -1058,6 +1058,7 @@ static hipError_t launch_ws(const ConvFwdArgs& a, hipStream_t st) {
   const int per_cu = 163840 / (int)lds >= 2 ? 2 : 1;  // resident blocks per CU (LDS-limited)
   int slots = 256 * per_cu / ncg;
   if (slots > ntiles) slots = ntiles;
+  if (a.grid_cap > 0 && a.grid_cap / ncg < slots) slots = a.grid_cap / ncg;  // single-op tests: several tiles per block
   if (slots < 1) slots = 1;
   char tag[96];
   std::snprintf(tag, sizeof(tag), "conv3x3_ws_kernel<%d, %d, %d, %d, %s>", NP, FN, TH, NW, FLIP ? "true" : "false");
@@ -1083,6 +1084,12 @@ static hipError_t launch_hs(const ConvFwdArgs& a, hipStream_t st) {
   // epilogue operands across tiles, 324 VGPRs, one block per CU)
   long long grid = (long long)ntiles * ncb;
   if (!FLIP && slots_env > 0 && grid > slots_env && slots_env % ncb == 0) grid = slots_env;
+  // single-op tests: a smaller cap, rounded down to a multiple of ncb (at least ncb, as launch_ws keeps at
+  // least one slot), so a small map still walks several tiles per block
+  if (!FLIP && a.grid_cap > 0) {
+    const long long cap = std::max(1, a.grid_cap / ncb) * (long long)ncb;
+    if (cap < grid) grid = cap;
+  }
   const bool mt = grid < (long long)ntiles * ncb;
   char tag[96];
   std::snprintf(tag, sizeof(tag), "conv3x3_hs_kernel<%d, %d, %d, %s, %s, %s>", FN, TH, NW, FLIP ? "true" : "false",
@@ -1109,9 +1116,9 @@ static hipError_t launch_halo_shape(const ConvFwdArgs& a, hipStream_t st) {
     if (!(C % 32 == 0 && C >= 128 && Co % 64 == 0)) return hipErrorNotSupported;
     // 32-channel blocks, 8 waves (two blocks per CU): enc2-4 downsample-block
     // dgrads 63 / 49 / 42 -> 56 / 40 / 35 us (Base, measured)
-    if (a.P % 16 == 0 && Co % 32 == 0) return launch_hs<2, 16, 8, true, true>(a, st);
-    const long long t16 = (long long)a.N * (a.P / 16) * (a.Q / 16) * (Co / 64);
-    if (a.P % 16 == 0 && t16 >= 256) return launch_hs<4, 16, 8, true, true>(a, st);
+    // (Co % 64 == 0 here, so every 16-row map takes the 32-channel blocks: the
+    // 64-channel 16-row instance that used to follow could not be selected)
+    if (a.P % 16 == 0) return launch_hs<2, 16, 8, true, true>(a, st);
     if (a.P % 8 == 0) return launch_hs<4, 8, 4, true, true>(a, st);
     return hipErrorNotSupported;
   }
@@ -1138,7 +1145,6 @@ static hipError_t launch_halo_shape(const ConvFwdArgs& a, hipStream_t st) {
   if (C == 96 && Co == 32 && a.P % 8 == 0) return launch_ws<3, 2, 8, 8, FLIP>(a, st);
   // halo-streamed: 256-pixel tiles while they still give >= ~1 block per CU
   if (C % 32 == 0 && C >= 128 && Co % 64 == 0) {
-    const long long t16 = (long long)a.N * (a.P / 16) * (a.Q / 16) * (Co / 64);
     // round 1 ran the C = 128 forwards (enc2, decoder3.3) as a 128x128 im2col
     // tile (faster than the 64-channel halo blocks then); the 32-channel
     // halo blocks below beat it (37-43 -> 31 us)
@@ -1146,12 +1152,13 @@ static hipError_t launch_halo_shape(const ConvFwdArgs& a, hipStream_t st) {
     // block's epilogue overlaps the other's MFMAs; measured on the Base
     // config: enc3/decoder4 dgrads -5..-7 %, enc4 -11..-19 %): 8 waves when
     // the grid is one round, else 4 waves with 4 rows each
-    if (a.P % 16 == 0 && Co % 32 == 0) {
+    // (Co % 64 == 0: every 16-row map lands here; the 64-channel 16-row
+    // instance that used to follow was unreachable and is gone)
+    if (a.P % 16 == 0) {
       const long long b32 = (long long)a.N * (a.P / 16) * (a.Q / 16) * (Co / 32);
       if (b32 <= 256) return launch_hs<2, 16, 8, FLIP, false>(a, st);
       return launch_hs<2, 16, 4, FLIP, false>(a, st);
     }
-    if (a.P % 16 == 0 && t16 >= 256) return launch_hs<4, 16, 8, FLIP, false>(a, st);
     if (a.P % 8 == 0) return launch_hs<4, 8, 4, FLIP, false>(a, st);
   }
   return hipErrorNotSupported;

@@ -2340,6 +2340,102 @@ int unet_conv3x3_fl(const void* x, int ldx, const void* wch, void* y, int ldy, c
   return 0;
 }
 
+const char* unet_last_kernel_tag(void) { return unet::last_kernel_tag(); }
+
+int unet_conv_ex(const unet_conv_ex_args* p, hipStream_t stream) {
+  conv_kernel_tag("");  // a refused call leaves no stale instance name behind
+  auto bad = [](const char* m) { set_err(std::string("unet_conv_ex: ") + m); return 1; };
+  if (!p || p->size != (int)sizeof(unet_conv_ex_args)) return bad("null argument or size != sizeof(unet_conv_ex_args)");
+  const unet_conv_ex_args& e = *p;
+  if (e.mode != 0 && e.mode != 1) return bad("mode must be 0 (forward) or 1 (data gradient)");
+  if (!e.x || !e.w || !e.y) return bad("x, w, y must be set");
+  if (e.N <= 0 || e.H <= 0 || e.W <= 0 || e.C <= 0 || e.P <= 0 || e.Q <= 0 || e.Cout <= 0 || e.R <= 0 || e.S <= 0 ||
+      e.stride <= 0 || e.pad < 0)
+    return bad("N, H, W, C, P, Q, Cout, R, S, stride must be positive");
+  if (e.C % 32 || e.Cout % 4) return bad("needs C % 32 == 0 and Cout % 4 == 0");
+  if (e.grid_cap < 0) return bad("grid_cap must be >= 0");
+  const bool fwd = e.mode == 0;
+  const bool bbany = e.act || e.yraw || e.mean || e.invstd || e.yraw2 || e.mean2 || e.invstd2 || e.bsums || e.bsums2 ||
+                     e.ldact || e.ldyraw || e.ldyraw2;
+  const bool foldany = e.gamma || e.beta || e.running_mean || e.running_var || e.eps != 0.f || e.relu;
+  const bool dsany = e.wds || e.yds || e.stats_ds || e.ldyds;
+  const bool x2any = e.x2 || e.w2 || e.C2 || e.ldx2;
+  const bool splitany = e.ysplit || e.ldysplit || e.csplit;
+  if (fwd && (bbany || x2any || splitany))
+    return bad("the fused BN backward, x2 / w2 and ysplit belong to the data gradient (mode 1)");
+  if (!fwd && (e.bias || e.stats || foldany || dsany))
+    return bad("bias, stats, the eval BN fold and wds / yds belong to the forward (mode 0)");
+  if (e.ldx < e.C) return bad("ldx < C");
+  if (e.ldy < (e.ysplit ? e.csplit : e.Cout)) return bad("ldy smaller than the channels stored to y");
+  if ((e.addend != nullptr) != (e.ldadd != 0) || (e.addend && e.ldadd < e.Cout)) return bad("addend needs ldadd >= Cout");
+  if (bbany) {
+    if (!e.bsums || !e.act || !e.yraw || !e.mean || !e.invstd || e.ldact < e.Cout || e.ldyraw < e.Cout)
+      return bad("the fused BN backward needs bsums, act, yraw, mean, invstd, ldact / ldyraw >= Cout");
+    const bool two = e.yraw2 || e.mean2 || e.invstd2 || e.bsums2 || e.ldyraw2;
+    if (two && (!e.yraw2 || !e.mean2 || !e.invstd2 || !e.bsums2 || e.ldyraw2 < e.Cout))
+      return bad("the two-BN form needs yraw2, mean2, invstd2, bsums2, ldyraw2 >= Cout");
+  }
+  if (x2any && (!e.x2 || !e.w2 || e.C2 <= 0 || e.ldx2 < e.C2)) return bad("x2 needs w2, C2 > 0, ldx2 >= C2");
+  if (splitany) {
+    if (!e.ysplit || e.csplit <= 0 || e.csplit >= e.Cout || e.ldysplit < e.Cout - e.csplit)
+      return bad("ysplit needs 0 < csplit < Cout and ldysplit >= Cout - csplit");
+    if (e.addend || bbany) return bad("ysplit does not combine with addend or the fused BN backward");
+  }
+  if (foldany) {
+    if (!e.gamma || !e.beta || !e.running_mean || !e.running_var || !(e.eps > 0.f))
+      return bad("the eval BN fold needs gamma, beta, running_mean, running_var, eps > 0 (relu only with them)");
+    if (e.stats) return bad("the eval BN fold does not combine with BN sums");
+  }
+  if (dsany && (!e.wds || !e.yds || e.ldyds < e.Cout)) return bad("wds needs yds, ldyds >= Cout");
+  if (e.chunk_major && (x2any || splitany || dsany)) return bad("the chunk-major launch has no x2, ysplit or wds");
+
+  ConvFwdArgs a = {};
+  a.x = (const bf16_t*)e.x; a.ldx = e.ldx; a.w = (const bf16_t*)e.w; a.y = (bf16_t*)e.y; a.ldy = e.ldy;
+  a.bias = e.bias; a.add = (const bf16_t*)e.addend; a.ldadd = e.ldadd; a.stats = e.stats;
+  a.N = e.N; a.H = e.H; a.W = e.W; a.C = e.C; a.P = e.P; a.Q = e.Q; a.Cout = e.Cout;
+  a.R = e.R; a.S = e.S; a.stride = e.stride; a.pad = e.pad;
+  a.grid_cap = e.grid_cap;
+  if (bbany) {
+    a.bb.act = (const bf16_t*)e.act; a.bb.ldact = e.ldact; a.bb.y = (const bf16_t*)e.yraw; a.bb.ldy = e.ldyraw;
+    a.bb.mean = e.mean; a.bb.invstd = e.invstd; a.bb.sums = e.bsums;
+    a.bb.npix = (int64_t)e.N * e.P * e.Q; a.bb.C = e.Cout; a.bb.relu = 1;
+    if (e.yraw2) {
+      a.bb.y2 = (const bf16_t*)e.yraw2; a.bb.ldy2 = e.ldyraw2; a.bb.mean2 = e.mean2; a.bb.invstd2 = e.invstd2;
+      a.bb.sums2 = e.bsums2;
+    }
+  }
+  if (x2any) { a.x2 = (const bf16_t*)e.x2; a.ldx2 = e.ldx2; a.w2 = (const bf16_t*)e.w2; a.C2 = e.C2; }
+  if (splitany) { a.ysplit = (bf16_t*)e.ysplit; a.ldysplit = e.ldysplit; a.csplit = e.csplit; }
+  if (foldany) {
+    a.fold.gamma = e.gamma; a.fold.beta = e.beta;
+    a.fold.run_mean = const_cast<float*>(e.running_mean); a.fold.run_var = const_cast<float*>(e.running_var);
+    a.fold.count = (double)e.N * e.P * e.Q; a.fold.C = e.Cout; a.fold.eps = e.eps; a.fold.training = 0;
+    a.fold_on = 1; a.fold_relu = e.relu ? 1 : 0;
+  }
+  auto refused = [&](hipError_t err) {
+    set_err(std::string("unet_conv_ex: the launcher refused this combination (") + hipGetErrorString(err) + ")");
+    return (int)err;
+  };
+  if (e.chunk_major) {  // only conv3x3_fl_kernel reads this pack
+    a.wch = a.w;
+    a.w = nullptr;
+    const hipError_t err = launch_conv3x3_fl(a, e.mode, stream);
+    return err == hipSuccess ? 0 : refused(err);
+  }
+  if (dsany) {  // as conv_fwd: folded where launch_conv_fwd folds; the executor would launch the two separately
+    a.wds = (const bf16_t*)e.wds; a.yds = (bf16_t*)e.yds; a.ldyds = e.ldyds; a.stats_ds = e.stats_ds;
+    if (!conv_fwd_ds_ok(a)) return bad("the downsample fold does not cover this shape / epilogue");
+    const hipError_t err = launch_conv_fwd(a, MODE_FWD, stream);
+    return err == hipSuccess ? 0 : refused(err);
+  }
+  if (e.R == 1 && e.S == 1 && e.stride == 1 && (fwd || !bbany)) {  // weight-stationary 1x1 where covered
+    const hipError_t err = launch_conv1x1(a, e.mode, stream);
+    if (err != hipErrorNotSupported) return err == hipSuccess ? 0 : refused(err);
+  }
+  const hipError_t err = launch_conv_fwd(a, fwd ? MODE_FWD : MODE_TRANS, stream);
+  return err == hipSuccess ? 0 : refused(err);
+}
+
 int unet_f8_quantize(const void* x, int ld, int C, int64_t npix, void* q, void* state, int calibrate,
                      hipStream_t stream) {
   CK(launch_f8_quant_act((const bf16_t*)x, ld, C, npix, (uint8_t*)q, (F8State*)state, calibrate, stream));

@@ -291,6 +291,7 @@ int wgrad_batch_grid();
 int wgrad_batch_maxseg(const WgBatchArgs& a);
 hipError_t launch_wgrad_batch(const WgBatchArgs& a, hipStream_t st);
 const char* last_kernel_tag();  // template instance of the last conv launch (profiler)
+void conv_kernel_tag(const char* tag);  // set by every conv launcher
 
 // ---- elementwise / reduction kernels (elementwise.hip) ----
 

@@ -234,6 +234,61 @@ int unet_conv3x3_fl(const void* x, int ldx, const void* wch, void* y, int ldy, c
 int unet_convt2x2(const void* x, int ldx, const void* w, void* y, int ldy, const float* bias, const void* act,
                   int ldact, const void* yraw, int ldyraw, const float* mean, const float* invstd, double* bsums,
                   double* bias_acc, int N, int H, int W, int Ci, int Co, int mode, int grid, hipStream_t stream);
+/* One conv launch with the WHOLE epilogue of the training / eval step, for
+ * single-op tests: the launch the executor's conv forward (mode 0) or conv data
+ * gradient (mode 1) would make, selected by the same dispatch.  The reference
+ * ops underneath are the torchvision BasicBlock convs and the decoder convs
+ * (advanced_models.py:72-100,197-205) with their BatchNorm2d folded in (eval) or
+ * differentiated (training backward).
+ * size = sizeof(unet_conv_ex_args) (checked).  A zero / null field switches the
+ * feature off; inconsistent combinations are rejected with a message before
+ * anything is launched, nothing is silently ignored.
+ *   w: the standard pack (unet_pack_weight kind 0 forward / kind 1 data
+ *      gradient); chunk_major != 0: the chunk-major pack (kind 5 / 6) and the
+ *      launch is conv3x3_fl_kernel's (unet_conv3x3_fl's shape rules).
+ *   N, H, W, C: the op's input grid and reduction channels (data gradient: dY);
+ *   P, Q, Cout: its output grid and channels (data gradient: dX).
+ *   mode 0: bias, addend, stats as unet_conv_fwd; gamma != null: the eval-mode
+ *      BN fold y = act((conv + bias) * scale + shift [+ addend]), scale = gamma /
+ *      sqrt(running_var + eps), shift = beta - running_mean * scale, act = ReLU
+ *      when relu != 0; wds != null: the block's 1x1 / stride-2 downsample folded
+ *      into this 3x3 / stride-2 forward, yds = conv1x1s2(x, wds) and its BN sums
+ *      stats_ds from the same launch (an error where the launcher does not fold).
+ *   mode 1: addend; bsums != null: the fused BN(+ReLU) backward as
+ *      unet_conv3x3_fl mode 1 (act, yraw, mean, invstd; yraw2, mean2, invstd2,
+ *      bsums2 for the two-BN form); x2 != null: the folded 1x1 / stride-2
+ *      downsample data gradient, output pixels (2p, 2q) += x2[n,p,q,:C2] . w2
+ *      (w2: kind-1 pack of the 1x1 weight); ysplit != null: output channels >=
+ *      csplit go to ysplit[pix * ldysplit + co - csplit].
+ *   grid_cap: 0 = the production grid; > 0 caps the grid of the kernels whose
+ *      blocks walk several tiles, rounded down to a whole number of output-
+ *      channel blocks and never below one tile slot: conv3x3_fl_kernel,
+ *      conv3x3_ws2_kernel, conv3x3_ws_kernel, conv1x1_kernel and the forward
+ *      conv3x3_hs_kernel.  The one-tile-per-block kernels have no grid to cap
+ *      and launch their full grid whatever grid_cap says: the data-gradient
+ *      conv3x3_hs_kernel, conv3x3s2_dgrad_kernel and the implicit GEMM
+ *      conv_glds_kernel (unet_last_kernel_tag tells which one ran).
+ * BN sums are only accumulated (no last-block finalisation), as in the other
+ * single-op entries. */
+typedef struct unet_conv_ex_args {
+  int size, mode, chunk_major, grid_cap;
+  int N, H, W, C, P, Q, Cout, R, S, stride, pad;
+  int ldx, ldy, ldadd, ldact, ldyraw, ldyraw2, ldx2, C2, ldysplit, csplit, ldyds, relu;
+  float eps;
+  const void* x; const void* w; void* y;
+  const float* bias; const void* addend; double* stats;
+  const void* act; const void* yraw; const float* mean; const float* invstd;
+  const void* yraw2; const float* mean2; const float* invstd2; double* bsums; double* bsums2;
+  const void* x2; const void* w2;
+  void* ysplit;
+  const float* gamma; const float* beta; const float* running_mean; const float* running_var;
+  const void* wds; void* yds; double* stats_ds;
+} unet_conv_ex_args;
+int unet_conv_ex(const unet_conv_ex_args* args, hipStream_t stream);
+/* the kernel template instance of the calling thread's last conv launch
+ * ("conv3x3_hs_kernel<2, 16, 8, true, false, false>", ...): tests assert which
+ * instance the dispatch selected */
+const char* unet_last_kernel_tag(void);
 /* ---- fp8 e4m3 forward conv (BASELINE.json configs[4]; no reference counterpart:
  * the reference's convs are fp32 torch.nn.Conv2d, advanced_models.py:72-100) ----
  * state: 16-B scale state {amax prev (float bits), amax this step, e8m0 code,
