@@ -3,14 +3,18 @@
 Drop-in for the hot path of SwagMag1213/image-segmentation-project
 (``advanced_models.UNetWithBackbone`` resnet34/no-attention, ``losses``
 bce/dice/combo, ``utils.calculate_metrics``, ``train.train_epoch/evaluate``),
+plus softmax losses and argmax metrics for mutually exclusive classes
+(``CrossEntropyLoss``, ``SoftmaxDiceLoss``, ``SoftmaxComboLoss``, ``confusion_matrix``),
 computed by hand-written gfx950 HIP kernels in ``libunet_hip.so`` (C ABI:
 ``include/unet_hip.h``).  The directory name carries hyphens, so import it with
 ``importlib.import_module("image-segmentation-project_amd")``.
 """
 from .advanced_models import UNetWithBackbone  # noqa: F401
-from .losses import BCELoss, ComboLoss, DiceLoss, get_loss_function  # noqa: F401
+from .losses import (BCELoss, ComboLoss, CrossEntropyLoss, DiceLoss, SoftmaxComboLoss,  # noqa: F401
+                     SoftmaxDiceLoss, get_loss_function)
 from .utils import (EarlyStopping, calculate_metrics, calculate_metrics_from_logits,  # noqa: F401
-                    calculate_metrics_per_class, calculate_metrics_per_class_from_logits, get_device)
+                    calculate_metrics_per_class, calculate_metrics_per_class_from_logits,
+                    calculate_multiclass_metrics, confusion_matrix, get_device, metrics_from_confusion)
 from .train import (evaluate, quick_train, train_epoch, train_model, TensorLoader,  # noqa: F401
                     GraphedTrainStep)
 from .synthetic import random_batch, synthetic_cells  # noqa: F401

@@ -15,6 +15,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # UNET_HIP_LIB: an alternative in-tree build for A/B measurements (scripts/)
 LIB_PATH = os.environ.get("UNET_HIP_LIB") or os.path.join(_HERE, "libunet_hip.so")
 LOSS_SCRATCH_LEN = 8 * 256  # UNET_LOSS_SCRATCH_LEN (include/unet_hip.h): per-block partials of the loss sums
+# softmax loss / confusion matrix geometry (UNET_SOFTMAX_* of include/unet_hip.h)
+SOFTMAX_MAX_CLASSES = 16
+SOFTMAX_SUMS_LEN = 52
+SOFTMAX_MAX_BLOCKS = 1024
+SOFTMAX_THREADS = 256
+SOFTMAX_SCRATCH_LEN = SOFTMAX_SUMS_LEN * SOFTMAX_MAX_BLOCKS
 
 _lib = None
 
@@ -76,6 +82,12 @@ SIGNATURES = {
     "unet_loss_backward": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_float, c_float, c_void_p, c_void_p,
                                    c_void_p, c_void_p]),
     "unet_mask_metrics": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    "unet_softmax_loss_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int, c_int,
+                                          c_float, c_float, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "unet_softmax_loss_backward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int, c_int,
+                                           c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "unet_confusion_matrix": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_int, c_void_p, c_void_p,
+                                      c_int64, c_void_p]),
     "unet_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float,
                                c_float, c_float, c_int, c_void_p]),
     "unet_allreduce_unique_id": (c_int, [c_void_p]),
@@ -168,6 +180,17 @@ def loss_buffers(device):
     unet_loss_forward / unet_mask_metrics call (one allocation)."""
     buf = torch.empty(8 + LOSS_SCRATCH_LEN, dtype=torch.float64, device=device)
     return buf[:8], buf[8:]
+
+
+def softmax_buffers(device):
+    """(sums [SOFTMAX_SUMS_LEN], scratch [SOFTMAX_SCRATCH_LEN]) fp64 device buffers
+    of one unet_softmax_loss_forward / unet_confusion_matrix call (one allocation)."""
+    buf = torch.empty(SOFTMAX_SUMS_LEN + SOFTMAX_SCRATCH_LEN, dtype=torch.float64, device=device)
+    return buf[:SOFTMAX_SUMS_LEN], buf[SOFTMAX_SUMS_LEN:]
+
+
+# label dtypes the softmax kernels read as they are -> label_dtype of the C ABI
+LABEL_DTYPES = {torch.uint8: 0, torch.int32: 1, torch.int64: 2}
 
 
 def ptr(t) -> int:

@@ -2234,6 +2234,93 @@ int unet_mask_metrics(const float* values, const float* target, int64_t n, int v
   return 0;
 }
 
+static_assert(UNET_SOFTMAX_MAX_CLASSES == kSmMaxK && UNET_SOFTMAX_SUMS_LEN == kSmSums &&
+                  UNET_SOFTMAX_MAX_BLOCKS == kSmSlots && UNET_SOFTMAX_THREADS == kSmNT,
+              "softmax loss geometry");
+static_assert((size_t)UNET_SOFTMAX_SCRATCH_LEN * sizeof(double) >=
+                  (size_t)kSmMaxK * kSmMaxK * kCmSlots * sizeof(unsigned),
+              "the confusion histograms fit the softmax scratch");
+
+// the argument checks shared by the three softmax entry points
+static bool softmax_args_ok(const char* fn, const void* logits, const void* labels, int label_dtype, int N, int K,
+                            int64_t HW) {
+  char m[200];
+  if (!logits || !labels) {
+    std::snprintf(m, sizeof(m), "%s: logits / labels is null", fn);
+  } else if (K < 2 || K > UNET_SOFTMAX_MAX_CLASSES) {
+    std::snprintf(m, sizeof(m), "%s: K = %d is outside 2..%d", fn, K, UNET_SOFTMAX_MAX_CLASSES);
+  } else if (label_dtype < 0 || label_dtype > 2) {
+    std::snprintf(m, sizeof(m), "%s: label_dtype %d is not 0 (uint8), 1 (int32) or 2 (int64)", fn, label_dtype);
+  } else if (N <= 0 || HW <= 0 || HW > ((int64_t)1 << 38) / N) {
+    // 2^38 pixels: the per-block uint32 histogram counts and the fp32 per-thread counts stay exact
+    std::snprintf(m, sizeof(m), "%s: N = %d, HW = %lld must be positive with N * HW <= 2^38", fn, N, (long long)HW);
+  } else {
+    return true;
+  }
+  set_err(m);
+  return false;
+}
+
+static bool softmax_kind_ok(const char* fn, int kind, const float* class_weights) {
+  char m[160];
+  if (kind < LOSS_BCE || kind > LOSS_COMBO) {
+    std::snprintf(m, sizeof(m), "%s: kind %d is not 0 (ce), 1 (dice) or 2 (combo)", fn, kind);
+  } else if (kind == LOSS_DICE && class_weights) {
+    std::snprintf(m, sizeof(m), "%s: class weights apply to the CE term; kind 1 (dice) takes none", fn);
+  } else {
+    return true;
+  }
+  set_err(m);
+  return false;
+}
+
+static bool softmax_scratch_ok(const char* fn, const void* scratch, int64_t scratch_len) {
+  if (scratch && scratch_len >= UNET_SOFTMAX_SCRATCH_LEN) return true;
+  char m[160];
+  std::snprintf(m, sizeof(m), "%s: scratch null or scratch_len %lld < UNET_SOFTMAX_SCRATCH_LEN (%d)", fn,
+                (long long)scratch_len, UNET_SOFTMAX_SCRATCH_LEN);
+  set_err(m);
+  return false;
+}
+
+int unet_softmax_loss_forward(const float* logits, const void* labels, int label_dtype, int N, int K, int64_t HW,
+                              const float* class_weights, int ignore_index, int kind, float alpha, float smooth,
+                              double* sums, double* scratch, int64_t scratch_len, float* loss_out,
+                              hipStream_t stream) {
+  const char* fn = "unet_softmax_loss_forward";
+  if (!softmax_args_ok(fn, logits, labels, label_dtype, N, K, HW) || !softmax_kind_ok(fn, kind, class_weights) ||
+      !softmax_scratch_ok(fn, scratch, scratch_len))
+    return 1;
+  if (!sums || !loss_out) { set_err("unet_softmax_loss_forward: sums / loss_out is null"); return 1; }
+  const SoftmaxArgs a{logits, labels, label_dtype, N, K, HW, class_weights, ignore_index};
+  CK(launch_softmax_loss_sums(a, kind, alpha, smooth, sums, scratch, loss_out, stream));
+  return 0;
+}
+
+int unet_softmax_loss_backward(const float* logits, const void* labels, int label_dtype, int N, int K, int64_t HW,
+                               const float* class_weights, int ignore_index, int kind, float alpha, float smooth,
+                               const double* sums, const float* grad_scale, float* dlogits, hipStream_t stream) {
+  const char* fn = "unet_softmax_loss_backward";
+  if (!softmax_args_ok(fn, logits, labels, label_dtype, N, K, HW) || !softmax_kind_ok(fn, kind, class_weights))
+    return 1;
+  if (!sums || !dlogits) { set_err("unet_softmax_loss_backward: sums / dlogits is null"); return 1; }
+  const SoftmaxArgs a{logits, labels, label_dtype, N, K, HW, class_weights, ignore_index};
+  CK(launch_softmax_loss_grad(a, kind, alpha, smooth, sums, grad_scale, dlogits, stream));
+  return 0;
+}
+
+int unet_confusion_matrix(const float* logits, const void* labels, int label_dtype, int N, int K, int64_t HW,
+                          int ignore_index, long long* cm, double* scratch, int64_t scratch_len,
+                          hipStream_t stream) {
+  const char* fn = "unet_confusion_matrix";
+  if (!softmax_args_ok(fn, logits, labels, label_dtype, N, K, HW) || !softmax_scratch_ok(fn, scratch, scratch_len))
+    return 1;
+  if (!cm) { set_err("unet_confusion_matrix: cm is null"); return 1; }
+  const SoftmaxArgs a{logits, labels, label_dtype, N, K, HW, nullptr, ignore_index};
+  CK(launch_confusion(a, cm, reinterpret_cast<unsigned*>(scratch), stream));
+  return 0;
+}
+
 int unet_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* step_coef,
                    int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
                    int advance_step, hipStream_t stream) {

@@ -438,6 +438,26 @@ hipError_t launch_loss_grad(const float* logits, const float* target, int64_t n,
                             int kind, float alpha, float smooth, const float* gscale, float* dl,
                             hipStream_t st);
 
+// softmax multi-class loss + confusion matrix (softmax_loss.hip).  logits fp32 NCHW
+// [N][K][HW], labels [N][HW] in label_dtype; class_weights: K floats or null.
+enum { SM_LABEL_U8 = 0, SM_LABEL_I32 = 1, SM_LABEL_I64 = 2 };
+constexpr int kSmMaxK = 16;
+constexpr int kSmNT = 256, kSmSlots = 1024;  // sums / grad block size; per-block partial slots of the sums
+constexpr int kCmNT = 512, kCmSlots = 256;  // confusion block size; per-block histogram slots
+// sums[0..52): ce_num, w_den, valid pixels, invalid labels, I[16], P[16], Y[16] (stride 16 whatever K is)
+constexpr int kSmSums = 4 + 3 * kSmMaxK;
+struct SoftmaxArgs {
+  const float* logits; const void* labels; int label_dtype; int N, K; int64_t HW;
+  const float* class_weights; int ignore_index;
+};
+// part: kSmSums * kSmSlots doubles (value-major per-block partials); kind: LOSS_BCE = CE, LOSS_DICE, LOSS_COMBO
+hipError_t launch_softmax_loss_sums(const SoftmaxArgs& a, int kind, float alpha, float smooth, double* sums,
+                                    double* part, float* out, hipStream_t st);
+hipError_t launch_softmax_loss_grad(const SoftmaxArgs& a, int kind, float alpha, float smooth, const double* sums,
+                                    const float* gscale, float* dl, hipStream_t st);
+// cm: int64 [K][K], row = true class, column = argmax; part: kSmMaxK^2 * kCmSlots uint32
+hipError_t launch_confusion(const SoftmaxArgs& a, long long* cm, unsigned* part, hipStream_t st);
+
 // fused Adam over flat fp32 buffers (optim.hip); coef = {step, step_size, sqrt(bc2)} on device
 hipError_t launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float* coef, float lr,
                        float beta1, float beta2, float eps, float wd, int advance_step, hipStream_t st);

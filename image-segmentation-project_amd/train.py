@@ -6,7 +6,9 @@ metrics from the pre-step logits in train-mode BN; batch-size-weighted means of
 per-batch metrics, train.py:38-68,89-112).  What changes is where the work
 runs: the model/criterion are the HIP path, the per-batch mask counts are one
 fused kernel on the logits, and the five ``.item()`` syncs per batch become one
-device->host copy per epoch.
+device->host copy per epoch.  With a softmax criterion and integer label-map
+masks ([N,H,W]) the per-batch record is the [K,K] confusion matrix instead, and
+the same keys come out with ``iou`` = mean IoU over the classes present.
 
 ``train_model`` keeps the epoch loop control of train.py:115-244 (ReduceLROnPlateau
 on val IoU, best-state deepcopy, EarlyStopping, returned dict) but takes
@@ -22,11 +24,26 @@ from typing import Dict, Optional
 
 import torch
 
-from .utils import EarlyStopping, mask_counts, metrics_from_counts
+from .utils import EarlyStopping, confusion_matrix, mask_counts, metrics_from_confusion, metrics_from_counts
+
+_METRIC_KEYS = ("precision", "recall", "f1", "iou", "accuracy")
 
 
-def _batch_record(logits, masks, loss, n):
-    counts = mask_counts(logits.detach(), masks, from_logits=True)[4:8]
+def _is_label_map(logits, masks) -> bool:
+    """Integer class map [N,H,W] / [N,1,H,W] for [N,K,H,W] logits (softmax
+    criteria), as opposed to float planes of the logits' own shape."""
+    if masks.is_floating_point() or masks.dtype == torch.bool or logits.dim() != 4 or logits.shape[1] < 2:
+        return False
+    return masks.dim() == 3 or (masks.dim() == 4 and masks.shape[1] == 1)
+
+
+def _batch_record(logits, masks, loss, n, criterion=None):
+    """Per-batch device record: tp/fp/fn/tn of the sigmoid mask, or for a label
+    map the [K,K] confusion matrix (ignore_index taken from the criterion)."""
+    if _is_label_map(logits, masks):
+        counts = confusion_matrix(logits.detach(), masks, getattr(criterion, "ignore_index", -100))
+    else:
+        counts = mask_counts(logits.detach(), masks, from_logits=True)[4:8]
     return counts, loss.detach().reshape(1).float(), n
 
 
@@ -39,9 +56,10 @@ def _finish(records, with_loss_key: bool) -> Dict:
     total = 0
     loss_sum = 0.0
     for (c, loss_v, (_, _, b)) in zip(counts, losses, records):
-        m = metrics_from_counts(*c)
-        for k, v in m.items():
-            out[k] += v * b
+        # [K,K] rows: a confusion matrix (iou = mIoU); else tp, fp, fn, tn
+        m = metrics_from_confusion(c) if isinstance(c[0], list) else metrics_from_counts(*c)
+        for k in _METRIC_KEYS:
+            out[k] += m[k] * b
         loss_sum += loss_v * b  # == loss.item() (fp32 value as Python float)
         total += b
     for k in list(out):
@@ -65,7 +83,7 @@ def train_epoch(model: torch.nn.Module, loader, optimizer: torch.optim.Optimizer
         loss.backward()
         optimizer.step()
         with torch.no_grad():
-            records.append(_batch_record(outputs, masks, loss, images.size(0)))
+            records.append(_batch_record(outputs, masks, loss, images.size(0), criterion))
     return _finish(records, with_loss_key=True)
 
 
@@ -79,7 +97,7 @@ def evaluate(model: torch.nn.Module, loader, device: torch.device, criterion: to
             masks = masks.to(device, non_blocking=True)
             outputs = model(images)
             loss = criterion(outputs, masks)
-            records.append(_batch_record(outputs, masks, loss, images.size(0)))
+            records.append(_batch_record(outputs, masks, loss, images.size(0), criterion))
     return _finish(records, with_loss_key=True)
 
 

@@ -73,6 +73,61 @@ def calculate_metrics_per_class_from_logits(logits, target) -> list:
     return _per_class(logits, target, from_logits=True)
 
 
+def confusion_matrix(logits, labels, ignore_index=-100):
+    """Device int64 ``[K,K]`` (row = true class, column = argmax of the logits,
+    lowest index on ties) of ``[N,K,H,W]`` logits and an integer label map
+    ``[N,H,W]`` / ``[N,1,H,W]``; labels equal to ``ignore_index`` or outside
+    ``[0,K)`` are not counted.  One HIP pass, exact integer counts, no host sync."""
+    from .losses import softmax_inputs
+    n, k, hw, labels = softmax_inputs(logits, labels)
+    _lib.require_gpu(logits)
+    x = logits.detach().contiguous().float()
+    y = labels.to(x.device).contiguous()
+    _, scratch = _lib.softmax_buffers(x.device)
+    cm = torch.empty((k, k), dtype=torch.int64, device=x.device)
+    _lib.check(_lib.load().unet_confusion_matrix(x.data_ptr(), y.data_ptr(), _lib.LABEL_DTYPES[y.dtype], n, k, hw,
+                                                 int(ignore_index), cm.data_ptr(), scratch.data_ptr(),
+                                                 scratch.numel(), _lib.stream_handle(x.device)),
+               "unet_confusion_matrix")
+    return cm
+
+
+def metrics_from_confusion(cm) -> dict:
+    """Metrics of a ``[K,K]`` confusion matrix (row = truth, column = prediction),
+    in Python floats on the host.  Per class one-vs-rest with the formulas of
+    ``metrics_from_counts``; ``precision`` / ``recall`` / ``f1`` are their macro
+    means, ``iou`` is the mean IoU over the classes that occur in the truth or
+    the prediction (tp + fp + fn > 0; 0.0 when there is none), ``accuracy`` is
+    trace / total; the per-class lists are under ``"per_class"``."""
+    rows = cm.detach().cpu().tolist() if isinstance(cm, torch.Tensor) else [list(r) for r in cm]
+    k = len(rows)
+    if k == 0 or any(len(r) != k for r in rows):
+        raise ValueError("metrics_from_confusion needs a square [K,K] matrix")
+    total = sum(sum(r) for r in rows)
+    per = {"precision": [], "recall": [], "f1": [], "iou": []}
+    present = []
+    for c in range(k):
+        tp = rows[c][c]
+        fp = sum(rows[r][c] for r in range(k)) - tp
+        fn = sum(rows[c]) - tp
+        m = metrics_from_counts(tp, fp, fn, total - tp - fp - fn)
+        for name in per:
+            per[name].append(m[name])
+        if tp + fp + fn > 0:
+            present.append(m["iou"])
+    out = {name: sum(per[name]) / k for name in ("precision", "recall", "f1")}
+    out["iou"] = sum(present) / len(present) if present else 0.0
+    out["accuracy"] = sum(rows[c][c] for c in range(k)) / (total + EPS)
+    out["per_class"] = per
+    return out
+
+
+def calculate_multiclass_metrics(logits, labels, ignore_index=-100) -> dict:
+    """``metrics_from_confusion(confusion_matrix(...))``: argmax metrics of
+    mutually exclusive classes (one device->host copy of K*K counts)."""
+    return metrics_from_confusion(confusion_matrix(logits, labels, ignore_index))
+
+
 def get_device():
     """utils.py:153-167 — the ROCm GPU when present (torch's 'cuda' device)."""
     if torch.cuda.is_available():

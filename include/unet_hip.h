@@ -13,6 +13,8 @@
  *   unet_loss_forward    BCELoss / DiceLoss / ComboLoss forward (losses.py:13-37,161-171)
  *   unet_loss_backward   their gradient wrt the logits
  *   unet_mask_metrics    calculate_metrics tp/fp/fn/tn counts (utils.py:120-151)
+ *   unet_softmax_loss_forward / _backward   softmax CE / multi-class Dice on integer label maps
+ *   unet_confusion_matrix                    argmax confusion matrix of the same inputs
  *   unet_adam_step       optimizer.step() of torch.optim.Adam(model.parameters(),
  *                        lr, weight_decay) (train.py:49,331-335)
  *   unet_conv_* / unet_maxpool_* / unet_bn_*   single ops of the graph above
@@ -131,6 +133,58 @@ int unet_loss_backward(const float* logits, const float* target, int64_t n, int 
  * scratch / scratch_len as for unet_loss_forward. */
 int unet_mask_metrics(const float* values, const float* target, int64_t n, int values_are_prob,
                       double* sums8, double* scratch, int64_t scratch_len, hipStream_t stream);
+
+/* ---- softmax multi-class loss + confusion matrix (mutually exclusive classes) ---- */
+/* logits: fp32, contiguous NCHW [N][K][HW] (the U-Net's multi-channel output),
+ *   K = 2..UNET_SOFTMAX_MAX_CLASSES.  Any 4-B aligned base is accepted: the
+ *   gradient and confusion kernels use 16-B accesses when HW % 4 == 0, logits
+ *   (and dlogits) are 16-B aligned and labels are aligned to 4 B (uint8) / 16 B
+ *   (int32, int64), and scalar ones otherwise; the results are bit-identical.
+ * labels: one integer per pixel, [N][HW], of label_dtype 0 = uint8, 1 = int32,
+ *   2 = int64 (read as they are: no conversion pass).  A pixel is valid when
+ *   0 <= label < K and label != ignore_index.  A label equal to ignore_index is
+ *   ignored; any other label outside [0, K) is ignored too and counted in
+ *   sums[3], so bad data can be detected (nothing faults).
+ * class_weights: K floats on the device, or null (all 1).  Not allowed with kind 1.
+ * kind: 0 CE   = ce_num / w_den  (F.cross_entropy(weight, ignore_index, "mean"))
+ *       1 Dice = 1 - (1/K) sum_k (2 I_k + smooth) / (P_k + Y_k + smooth): one
+ *                global Dice per class over the valid pixels of the batch
+ *       2 alpha * CE + (1 - alpha) * Dice
+ *   With no valid pixel (w_den == 0) CE contributes 0 and its gradient is 0
+ *   (torch returns NaN there, which would poison a replayed optimizer step).
+ * sums: UNET_SOFTMAX_SUMS_LEN doubles out:
+ *   [0] ce_num = sum w[y] nll   [1] w_den = sum w[y]   [2] valid pixels
+ *   [3] labels outside [0, K) other than ignore_index
+ *   [4 + k] I_k = sum p_k [y = k]   [20 + k] P_k = sum p_k   [36 + k] Y_k = sum [y = k]
+ *   (k < K; the entries of k >= K are written as 0), all over valid pixels.
+ * scratch: caller-owned device memory of scratch_len >= UNET_SOFTMAX_SCRATCH_LEN
+ *   doubles (8-B aligned) for per-block partials, added in block order by a
+ *   second launch: no atomics on memory, the results are bit-reproducible.
+ *   Nothing needs zeroing.  The sums kernel uses at most UNET_SOFTMAX_MAX_BLOCKS
+ *   blocks of UNET_SOFTMAX_THREADS threads, one pixel per thread and stride.
+ * Every call validates its arguments (K, label_dtype, kind, null pointers,
+ * scratch_len, N / HW > 0, weights with kind 1) before launching anything, and
+ * allocates and synchronises nothing: all three are graph-capturable. */
+#define UNET_SOFTMAX_MAX_CLASSES 16
+#define UNET_SOFTMAX_SUMS_LEN 52
+#define UNET_SOFTMAX_MAX_BLOCKS 1024
+#define UNET_SOFTMAX_THREADS 256
+#define UNET_SOFTMAX_SCRATCH_LEN (UNET_SOFTMAX_SUMS_LEN * UNET_SOFTMAX_MAX_BLOCKS)
+int unet_softmax_loss_forward(const float* logits, const void* labels, int label_dtype, int N, int K, int64_t HW,
+                              const float* class_weights, int ignore_index, int kind, float alpha, float smooth,
+                              double* sums, double* scratch, int64_t scratch_len, float* loss_out,
+                              hipStream_t stream);
+/* dlogits [N][K][HW] = grad_scale[0] * dL/dlogits (grad_scale: device scalar, or
+ * null for 1), from the sums of the forward call on the same inputs.  Every
+ * element is written; all channels of an ignored pixel get an exact 0. */
+int unet_softmax_loss_backward(const float* logits, const void* labels, int label_dtype, int N, int K, int64_t HW,
+                               const float* class_weights, int ignore_index, int kind, float alpha, float smooth,
+                               const double* sums, const float* grad_scale, float* dlogits, hipStream_t stream);
+/* cm: int64 [K][K] out, cm[t][p] = valid pixels of true class t whose first
+ * maximum logit is channel p (lowest index on ties).  Exact integer counts. */
+int unet_confusion_matrix(const float* logits, const void* labels, int label_dtype, int N, int K, int64_t HW,
+                          int ignore_index, long long* cm, double* scratch, int64_t scratch_len,
+                          hipStream_t stream);
 
 /* ---- optimizer ---- */
 /* One Adam step (coupled L2 weight decay, torch.optim.Adam semantics) over n
