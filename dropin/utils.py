@@ -9,3 +9,4 @@ if _REPO not in _sys.path:
     _sys.path.insert(0, _REPO)
 
 from image_segmentation_project_amd.utils import *  # noqa: E402,F401,F403
+from image_segmentation_project_amd.predict import predict, tile_origins  # noqa: E402,F401  (whole-frame inference)

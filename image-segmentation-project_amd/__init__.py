@@ -4,7 +4,8 @@ Drop-in for the hot path of SwagMag1213/image-segmentation-project
 (``advanced_models.UNetWithBackbone`` resnet34/no-attention, ``losses``
 bce/dice/combo, ``utils.calculate_metrics``, ``train.train_epoch/evaluate``),
 plus softmax losses and argmax metrics for mutually exclusive classes
-(``CrossEntropyLoss``, ``SoftmaxDiceLoss``, ``SoftmaxComboLoss``, ``confusion_matrix``),
+(``CrossEntropyLoss``, ``SoftmaxDiceLoss``, ``SoftmaxComboLoss``, ``confusion_matrix``)
+and tiled whole-frame inference on frames of any size (``predict``),
 computed by hand-written gfx950 HIP kernels in ``libunet_hip.so`` (C ABI:
 ``include/unet_hip.h``).  The directory name carries hyphens, so import it with
 ``importlib.import_module("image-segmentation-project_amd")``.
@@ -20,6 +21,7 @@ from .train import (evaluate, quick_train, train_epoch, train_model, TensorLoade
 from .synthetic import random_batch, synthetic_cells  # noqa: F401
 from . import dataset  # noqa: F401
 from .dataset import CellAugmenter, CellSegmentationDataset, prepare_data, preprocess  # noqa: F401
+from .predict import predict, tile_origins  # noqa: F401
 from . import ddp  # noqa: F401
 from . import optim  # noqa: F401
 from .optim import Adam  # noqa: F401

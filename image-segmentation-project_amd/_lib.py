@@ -21,6 +21,7 @@ SOFTMAX_SUMS_LEN = 52
 SOFTMAX_MAX_BLOCKS = 1024
 SOFTMAX_THREADS = 256
 SOFTMAX_SCRATCH_LEN = SOFTMAX_SUMS_LEN * SOFTMAX_MAX_BLOCKS
+TILE_MAX = 1024  # UNET_TILE_MAX: largest tile of unet_tile_gather / unet_tile_blend
 
 _lib = None
 
@@ -130,6 +131,9 @@ SIGNATURES = {
     "unet_mask_prep": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "unet_normalize_microscopy": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "unet_rot90_vflip_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "unet_tile_grid": (c_int, [c_int] * 4 + [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "unet_tile_gather": (c_int, [c_void_p] + [c_int] * 5 + [ctypes.c_uint, c_int64, c_int64, c_void_p, c_void_p]),
+    "unet_tile_blend": (c_int, [c_void_p] + [c_int] * 6 + [ctypes.c_uint, c_void_p, c_void_p, c_void_p, c_void_p]),
     "unet_maxpool_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
     "unet_maxpool_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 4 + [c_void_p]),
 }

@@ -335,11 +335,20 @@ class UNetWithBackbone(nn.Module):
         ba = (ctypes.c_void_p * len(bufs))(*[b.data_ptr() for b in bufs])
         return pa, ba
 
-    def _run_forward(self, plan, x, training: bool):
+    def _run_forward(self, plan, x, training: bool, out=None):
+        """``out``: an optional contiguous fp32 [N, n_classes, H, W] tensor on x's
+        device that receives the logits (``predict`` writes each tile batch
+        straight into its tile-logit buffer); default: a fresh tensor."""
         _lib.require_gpu(x)
         x = x.contiguous().float()
         n, _, h, w = x.shape
-        logits = torch.empty((n, self.n_classes, h, w), dtype=torch.float32, device=x.device)
+        if out is None:
+            logits = torch.empty((n, self.n_classes, h, w), dtype=torch.float32, device=x.device)
+        else:
+            if (tuple(out.shape) != (n, self.n_classes, h, w) or out.dtype != torch.float32
+                    or out.device != x.device or not out.is_contiguous()):
+                raise ValueError(f"out must be contiguous fp32 {(n, self.n_classes, h, w)} on {x.device}")
+            logits = out
         pa, ba = self._pointer_arrays()
         plan.generation += 1
         rc = plan.lib.unet_forward(plan.handle, x.data_ptr(), pa, ba, plan.workspace.data_ptr(), logits.data_ptr(),

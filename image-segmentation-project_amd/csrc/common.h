@@ -56,6 +56,18 @@ using unet::kTimSlots;
 
 #define LDS_PTR(T, p) ((__attribute__((address_space(3))) T*)(p))
 
+// The project's mask rule: sigmoid_cpu(v) > 0.5 exactly when
+// bits(v) >= 0x33C00001 for non-negative v (loss_sums, tile_blend_kernel)
+constexpr float kMaskThreshold = 8.94069742685133e-08f;
+__device__ __forceinline__ bool mask_positive(float v) { return v >= kMaskThreshold; }
+
+// BORDER_REFLECT_101 index into [0, n)
+__device__ __forceinline__ int reflect101(int i, int n) {
+  if (n == 1) return 0;
+  while (i < 0 || i >= n) i = i < 0 ? -i : 2 * n - 2 - i;
+  return i;
+}
+
 __device__ __forceinline__ float bf2f(bf16_t v) {
   return __uint_as_float(((unsigned)v) << 16);
 }

@@ -160,13 +160,6 @@ __device__ __forceinline__ int clip_trunc(int v, double plo, double phi) {
   return (int)c;
 }
 
-// BORDER_REFLECT_101 index into [0, n)
-__device__ __forceinline__ int reflect101(int i, int n) {
-  if (n == 1) return 0;
-  while (i < 0 || i >= n) i = i < 0 ? -i : 2 * n - 2 - i;
-  return i;
-}
-
 constexpr int kGrid = 8;
 
 struct NormSmem {

@@ -14,8 +14,6 @@
 
 namespace unet {
 
-constexpr float kMaskThreshold = 8.94069742685133e-08f;  // 0x33C00001, SURVEY.md §0
-
 // grid cap of the BN apply kernels (each block recomputes the per-channel
 // coefficients in its prologue; fewer, longer blocks amortise that and keep
 // the next pass's loads in flight).  256 = 1 block per CU: since split-K
@@ -1849,7 +1847,7 @@ __device__ __forceinline__ void loss_accum(float v, float y, int from_prob, floa
     s[1] += sg * y;
     s[2] += sg;
     s[3] += y;
-    pred = v >= kMaskThreshold ? 1.f : 0.f;  // == (sigmoid_cpu(v) > 0.5)
+    pred = mask_positive(v) ? 1.f : 0.f;  // == (sigmoid_cpu(v) > 0.5)
   } else {
     pred = v > 0.5f ? 1.f : 0.f;
   }

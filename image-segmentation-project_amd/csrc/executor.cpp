@@ -2680,6 +2680,70 @@ int unet_filter2d_u8(const uint8_t* src, int N, int H, int W, const float* kerne
   return 0;
 }
 
+// ---- tiled whole-frame inference (tile.hip) ----
+// the argument checks shared by the tile entry points; fills g
+static bool tile_args_ok(const char* fn, int N, int H, int W, int T, int overlap, unsigned tta, TileGeom* g) {
+  char m[200];
+  if (N <= 0 || H <= 0 || W <= 0) {
+    std::snprintf(m, sizeof(m), "%s: N = %d, H = %d, W = %d must be positive", fn, N, H, W);
+  } else if (T <= 0 || T > UNET_TILE_MAX) {
+    std::snprintf(m, sizeof(m), "%s: T = %d is outside 1..%d", fn, T, UNET_TILE_MAX);
+  } else if (overlap < 0 || 2 * overlap > T) {
+    std::snprintf(m, sizeof(m), "%s: overlap = %d is outside [0, T/2] (T = %d)", fn, overlap, T);
+  } else if (tta == 0 || tta > 0xFFu) {
+    std::snprintf(m, sizeof(m), "%s: tta = 0x%X is not a non-empty mask of the 8 dihedral transforms", fn, tta);
+  } else if (!tile_geom(H, W, T, overlap, tta, N, g)) {
+    std::snprintf(m, sizeof(m), "%s: bad tile geometry", fn);
+  } else {
+    return true;
+  }
+  set_err(m);
+  return false;
+}
+
+int unet_tile_grid(int H, int W, int T, int overlap, int* ny, int* nx) {
+  if (!ny || !nx) { set_err("unet_tile_grid: ny / nx is null"); return 1; }
+  if (H <= 0 || W <= 0 || T <= 0 || overlap < 0 || 2 * (int64_t)overlap > T) {
+    char m[200];
+    std::snprintf(m, sizeof(m), "unet_tile_grid: H = %d, W = %d, T = %d must be positive and overlap = %d in [0, T/2]",
+                  H, W, T, overlap);
+    set_err(m);
+    return 1;
+  }
+  *ny = tile_axis_count(H, T, T - overlap);
+  *nx = tile_axis_count(W, T, T - overlap);
+  return 0;
+}
+
+int unet_tile_gather(const float* image, int N, int H, int W, int T, int overlap, unsigned tta, int64_t first,
+                     int64_t count, float* tiles, hipStream_t stream) {
+  const char* fn = "unet_tile_gather";
+  if (!image || !tiles) { set_err("unet_tile_gather: image / tiles is null"); return 1; }
+  TileGeom g;
+  if (!tile_args_ok(fn, N, H, W, T, overlap, tta, &g)) return 1;
+  if (first < 0 || count < 0) { set_err("unet_tile_gather: first / count is negative"); return 1; }
+  CK(launch_tile_gather(image, tiles, g, first, count, stream));
+  return 0;
+}
+
+int unet_tile_blend(const float* tile_logits, int N, int K, int H, int W, int T, int overlap, unsigned tta,
+                    float* logits, uint8_t* mask, uint8_t* labels, hipStream_t stream) {
+  const char* fn = "unet_tile_blend";
+  if (!tile_logits) { set_err("unet_tile_blend: tile_logits is null"); return 1; }
+  if (!logits && !mask && !labels) { set_err("unet_tile_blend: logits, mask and labels are all null"); return 1; }
+  if (K < 1 || K > UNET_TILE_MAX_CLASSES) {
+    char m[120];
+    std::snprintf(m, sizeof(m), "unet_tile_blend: K = %d is outside 1..%d", K, UNET_TILE_MAX_CLASSES);
+    set_err(m);
+    return 1;
+  }
+  if (labels && K == 1) { set_err("unet_tile_blend: labels (argmax) need K >= 2"); return 1; }
+  TileGeom g;
+  if (!tile_args_ok(fn, N, H, W, T, overlap, tta, &g)) return 1;
+  CK(launch_tile_blend(tile_logits, logits, mask, labels, g, N, K, stream));
+  return 0;
+}
+
 // ---------------------------------------------------------------------------
 // DDP gradient reduction over RCCL for non-Python hosts (SURVEY.md §8(b):
 // "unet_allreduce_* ... communicator init from a ncclUniqueId byte blob";

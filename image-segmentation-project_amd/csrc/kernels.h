@@ -477,6 +477,32 @@ hipError_t launch_filter2d(const uint8_t* src, uint8_t* dst, int N, int H, int W
 hipError_t launch_rot90_vflip(const uint8_t* src, uint8_t* dst, int N, int H, int W, const int* k, const int* flip,
                               hipStream_t st);
 
+// tiled whole-frame inference (tile.hip): the tile geometry of one call.  Per
+// axis of length L with tiles T, stride S = T - O: one centred tile when L <= T,
+// otherwise ceil((L - T) / S) + 1 tiles at j S (j < n - 1) and L - T.
+struct TileGeom {
+  int H, W, T, O, S, ny, nx, M;
+  unsigned tta;    // bit d = dihedral transform d = k + 4 flip; M = popcount
+  int64_t total;   // N * M * ny * nx tiles, flat index t = ((n M + m) ny + jy) nx + jx
+};
+__host__ __device__ inline int tile_axis_count(int L, int T, int S) { return L <= T ? 1 : (L - T + S - 1) / S + 1; }
+__host__ __device__ inline int tile_origin(int j, int n, int L, int T, int S) {
+  if (L <= T) return -((T - L) / 2);
+  return j < n - 1 ? j * S : L - T;
+}
+// 1-D blend weight of footprint position i: min(i + 1, T - i, O + 1)
+__host__ __device__ inline int tile_w1(int i, int T, int O) {
+  const int a = i + 1 < T - i ? i + 1 : T - i;
+  return a < O + 1 ? a : O + 1;
+}
+// false: H, W, T, N <= 0, overlap outside [0, T/2], tta outside 1..0xFF
+bool tile_geom(int H, int W, int T, int overlap, unsigned tta, int N, TileGeom* g);
+hipError_t launch_tile_gather(const float* image, float* tiles, const TileGeom& g, int64_t first, int64_t count,
+                              hipStream_t st);
+// logits / mask / labels: each may be null
+hipError_t launch_tile_blend(const float* tile_logits, float* logits, uint8_t* mask, uint8_t* labels,
+                             const TileGeom& g, int N, int K, hipStream_t st);
+
 // attention decoder (attention.hip; advanced_models.py:7-61)
 struct AttGateArgs {
   const bf16_t* s; int lds;            // relu(BN_g + BN_x), F_int channels

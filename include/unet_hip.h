@@ -422,6 +422,42 @@ int unet_warp_affine_u8(const uint8_t* src, int N, int H, int W, const double* m
 int unet_filter2d_u8(const uint8_t* src, int N, int H, int W, const float* kernels, const int* ksize, uint8_t* dst,
                      hipStream_t stream);
 
+/* ---- tiled whole-frame inference (no reference counterpart: the reference
+ * predicts at the training size only) ----
+ * Geometry shared by the three entries.  Square tiles T x T (1..UNET_TILE_MAX),
+ * overlap 0 <= overlap <= T/2, stride S = T - overlap.  Per axis of length L:
+ *   L <= T: one tile at origin -((T - L) / 2); the footprint outside the image
+ *           reads BORDER_REFLECT_101 (L == 1: index 0);
+ *   L >  T: n = ceil((L - T) / S) + 1 tiles at j S (j < n - 1) and L - T.
+ * At most 3 tiles cover a pixel per axis.  Blend weight of footprint position
+ * (u, v): the integer w1(u) w1(v), w1(i) = min(i + 1, T - i, overlap + 1).
+ * tta: non-zero 8-bit mask of dihedral transforms d = k + 4 flip, "np.rot90(a, k),
+ * then [::-1] if flip" (unet_rot90_vflip_u8's convention) applied to the tile
+ * content; M = popcount(tta), m = rank of d among the set bits.  Flat tile index
+ * t = ((n M + m) ny + jy) nx + jx, total = N M ny nx.  T need not be a multiple
+ * of 32 (that is the model's constraint). */
+#define UNET_TILE_MAX 1024        /* keeps the int32 weight sum <= 72 * 513^2 */
+#define UNET_TILE_MAX_CLASSES 16
+/* host-only: tiles per axis for the geometry above; error on T <= 0, overlap < 0 or > T/2 */
+int unet_tile_grid(int H, int W, int T, int overlap, int* ny, int* nx);
+/* image fp32 [N][H][W] -> tiles fp32 [count][T][T] for the flat indices
+ * [first, first + count); slots with t >= total are written as zeros (the
+ * zero-filled tail of a fixed-size batch).  16-B aligned `tiles` with T % 4 == 0
+ * stores 16 B per lane. */
+int unet_tile_gather(const float* image, int N, int H, int W, int T, int overlap, unsigned tta,
+                     int64_t first, int64_t count, float* tiles, hipStream_t stream);
+/* tile_logits fp32 [total][K][T][T] (K = 1..UNET_TILE_MAX_CLASSES) -> per image
+ * pixel and class  out = (sum_t w_t v_t) / (float)(sum_t w_t)  over the covering
+ * tiles in ascending t, v_t read back through the inverse transform; fp32
+ * multiply and add kept apart, from 0; int32 weight sum; correctly rounded
+ * division: bit-reproducible, no atomics.  Outputs of the one pass, each may be
+ * null (not all three): logits fp32 [N][K][H][W]; mask uint8 [N][K][H][W] =
+ * bits(out) >= 0x33C00001 for non-negative out (unet_mask_metrics' predicate);
+ * labels uint8 [N][H][W] = argmax over K, lowest class on ties
+ * (unet_confusion_matrix' rule; needs K >= 2). */
+int unet_tile_blend(const float* tile_logits, int N, int K, int H, int W, int T, int overlap, unsigned tta,
+                    float* logits, uint8_t* mask, uint8_t* labels, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
