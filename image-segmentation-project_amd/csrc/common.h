@@ -183,36 +183,6 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
 }
 
-// Last-arriver election across the blocks of one launch
-// (cdna_hip_programming.md §6 Guideline 16, counter form): every wave drains
-// its own atomics/stores, one lane releases at agent scope and takes a ticket;
-// the block that draws total-1 acquires and may read everybody's results.
-// `flag` must be a word of the DYNAMIC LDS region (no second __shared__ object
-// beside an LDS-DMA staging array: §5 trap 4(a)).
-// The published data are device-scope fp64 atomic adds, which execute at the
-// memory side ("8-B agent atomics both sides", MI355X_MICROARCH.md Valid
-// forms): the waves that issued them only drain their own vmcnt — no L2
-// write-back release fence per block.
-__device__ __forceinline__ bool last_block_arrive(unsigned* ticket, unsigned total, int* flag,
-                                                  bool issued_atomics) {
-  if (issued_atomics) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned prev = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *flag = prev == total - 1 ? 1 : 0;
-  }
-  __syncthreads();
-  const bool last = *flag != 0;
-  if (last) {
-    if (threadIdx.x == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();
-  }
-  return last;
-}
-
 // BatchNorm per-channel statistics are fp64 sums (sum, sumsq) so that
 // var = E[y^2]-mean^2 does not cancel: stats[0..C) = sum, stats[C..2C) = sumsq.
 // Per-channel affine form of BN: y_hat*gamma+beta == y*scale + shift.
@@ -244,17 +214,14 @@ __device__ __forceinline__ void bn_scale_shift(const unet::BnLaunch& p, int c, f
   var_out = var;
 }
 
-// Training-mode finalisation of one BN layer (run by ONE block): scale/shift
-// for the consumers, batch mean/invstd for the backward, running stats with
-// momentum and the unbiased variance (torch.nn.BatchNorm2d semantics).
-__device__ __forceinline__ void bn_finalize(const unet::BnLaunch& p) {
-  for (int c = threadIdx.x; c < p.C; c += blockDim.x) {
+// Training-mode finalisation of channels [cbeg, cend) of one BN layer, run by
+// ONE block per channel (block 0 of a consumer of the batch sums): batch
+// mean/invstd for the backward, running stats with momentum and the unbiased
+// variance (torch.nn.BatchNorm2d semantics).
+__device__ __forceinline__ void bn_finalize(const unet::BnLaunch& p, int cbeg, int cend) {
+  for (int c = cbeg + threadIdx.x; c < cend; c += blockDim.x) {
     float sc, sh, m, inv, var;
     bn_scale_shift(p, c, sc, sh, m, inv, var);
-    if (p.ss) {
-      p.ss[c] = sc;
-      p.ss[p.C + c] = sh;
-    }
     if (p.training) {
       p.save_mean[c] = m;
       p.save_invstd[c] = inv;
@@ -270,10 +237,9 @@ __device__ __forceinline__ void bn_finalize(const unet::BnLaunch& p) {
 // Per-channel BN-backward apply coefficients from the replica sums:
 // dY = A dZ + B y + C, A = k1 = gamma invstd, B = -k1 invstd m2,
 // C = k1 (invstd m2 mu - m1), m1 = mean dZ, m2 = mean dZ xhat.  Shared by
-// bn_bwd_apply_kernel (both coefficient sources: replica sums, or the
-// finalised k1 / m1 / m2 of a ticket), the BN-fused weight gradients and the
-// stem's fused apply (side products must be bit-identical to the apply
-// pass): no contraction, fixed order (bn_bwd_coef_abc).
+// bn_bwd_apply_kernel, the BN-fused weight gradients and the stem's fused
+// apply (side products must be bit-identical to the apply pass): no
+// contraction, fixed order (bn_bwd_coef_abc).
 __device__ __forceinline__ void bn_bwd_coef_abc(float k1, float m1, float m2, float is, float mu, float& A, float& B,
                                                 float& C) {
   // explicit round-to-nearest operations: no context-dependent contraction
@@ -294,34 +260,6 @@ __device__ __forceinline__ void bn_bwd_apply_coef(const unet::BnBwdArgs& a, int 
   const float k1 = __fmul_rn(a.gamma[ch], a.invstd[ch]);
   const float m1 = (float)__dmul_rn(s1, inv_n), m2 = (float)__dmul_rn(s2, inv_n);
   bn_bwd_coef_abc(k1, m1, m2, a.invstd[ch], a.mean[ch], A, B, C);
-}
-
-// Last block of a BN-backward reduction (bn_bwd_reduce_kernel or a fused
-// conv-dgrad epilogue): per-channel coefficients of the apply pass and the
-// parameter gradients dgamma = sum dZ*xhat, dbeta = sum dZ.
-__device__ __forceinline__ void bn_bwd_finalize(const unet::BnBwdArgs& a) {
-  const bool two = a.y2 != nullptr;
-  const double inv_n = 1.0 / (double)a.npix;
-  for (int c = threadIdx.x; c < a.C; c += blockDim.x) {
-    double s1 = 0.0, s2 = 0.0, t2 = 0.0;
-    for (int r = 0; r < unet::kStatRep; ++r) {
-      const size_t rep = (size_t)r * 2 * a.C;
-      s1 += a.sums[rep + c];
-      s2 += a.sums[rep + a.C + c];
-      if (two) t2 += a.sums2[rep + a.C + c];
-    }
-    a.coef[c] = a.gamma[c] * a.invstd[c];
-    a.coef[a.C + c] = (float)(s1 * inv_n);
-    a.coef[2 * a.C + c] = (float)(s2 * inv_n);
-    a.dgamma[c] = (float)s2;
-    a.dbeta[c] = (float)s1;
-    if (two) {
-      a.coef[3 * a.C + c] = a.gamma2[c] * a.invstd2[c];
-      a.coef[4 * a.C + c] = (float)(t2 * inv_n);
-      a.dgamma2[c] = (float)t2;
-      a.dbeta2[c] = (float)s1;  // same dZ feeds both BNs
-    }
-  }
 }
 
 // dW index of element e of slab unit u (SlabLayout), -1 if that accumulator

@@ -266,14 +266,6 @@ __global__ void __launch_bounds__(kNW * 64) conv3x3_fl_kernel(ConvFwdArgs a, int
     if (stats) {  // the loaders' reduction barriers
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_s_barrier();
-      const unsigned* tk = fbwd ? a.bb.ticket : a.bn.ticket;
-      if (tk) {
-        int* flag = reinterpret_cast<int*>(smem + kOffH0 + 32 * kCOT * 3 * sizeof(float));
-        if (last_block_arrive(const_cast<unsigned*>(tk), gridDim.x, flag, false)) {
-          if (fbwd) bn_bwd_finalize(a.bb);
-          else bn_finalize(a.bn);
-        }
-      }
     }
     return;
   }
@@ -326,7 +318,13 @@ __global__ void __launch_bounds__(kNW * 64) conv3x3_fl_kernel(ConvFwdArgs a, int
   issue_w(0, 0);
   issue_h(0, 0);
   TSTAMP_TH(a.tim, 24, LT);
-  if (lt < kCOT) {  // per-channel epilogue constants of the block's output channels
+  // per-channel epilogue constants of the block's output channels, by loader
+  // wave 0 (lt < kCOT).  The test is on the wave id, a scalar branch: a
+  // per-lane `lt < kCOT` is an exec-masked region whose join sits where the
+  // loaders spill, and hipcc has placed VGPR spill stores in that join before
+  // the exec restore (waves 1-3 arrive there with exec = 0 and never store)
+  static_assert(kCOT == 64, "loader wave 0 = loader threads 0..kCOT-1");
+  if (lw == 0) {
     const int c = lt, co = cob * kCOT + c;
     float b = a.bias ? a.bias[co] : 0.f, c1 = 0.f, c2 = 0.f, c3 = 0.f, c4 = 0.f;
     if (fold) {
@@ -526,14 +524,6 @@ __global__ void __launch_bounds__(kNW * 64) conv3x3_fl_kernel(ConvFwdArgs a, int
     else atomicAdd((fbwd ? a.bb.sums : a.stats) + rep + which * a.Cout + co, (double)tsum);
   }
   __builtin_amdgcn_s_barrier();  // R2
-  const unsigned* tk = fbwd ? a.bb.ticket : a.bn.ticket;
-  if (tk) {
-    int* flag = reinterpret_cast<int*>(smem + kOffH0 + 32 * kCOT * 3 * sizeof(float));
-    if (last_block_arrive(const_cast<unsigned*>(tk), gridDim.x, flag, lt < 3 * kCOT)) {
-      if (fbwd) bn_bwd_finalize(a.bb);
-      else bn_finalize(a.bn);
-    }
-  }
   TSTAMP_TH(a.tim, 22, LT);
   TSTAMP_RT_TH(a.tim, 31, LT);
 }
@@ -719,7 +709,7 @@ __global__ void __launch_bounds__(kNW * 64) conv3x3_ws2_kernel(ConvFwdArgs a, in
 #pragma unroll
       for (int e = 0; e < 4; ++e) q0[i][e] = q1[i][e] = 0.f;
     if constexpr (XF) {
-      if (blockIdx.x == 0) bn_finalize(a.xbn);  // saved mean / invstd, running statistics (wave 0)
+      if (blockIdx.x == 0) bn_finalize(a.xbn, 0, a.xbn.C);  // saved mean / invstd, running statistics (wave 0)
       __builtin_amdgcn_s_barrier();             // X: the loaders' scale / shift table is in LDS
     }
     TSTAMP(a.tim, 1);
@@ -1036,8 +1026,6 @@ bool conv3x3_ws2_ok(const ConvFwdArgs& a, bool flip) {
   const char* ev = std::getenv("UNET_NO_WS2");
   const bool off = ev && (ev[0] == '1' || (ev[0] == 'f' && !flip) || (ev[0] == 'b' && flip) ||
                           (ev[0] == 'x' && !flip && a.xform));
-  // (the last-block BN finalisation, UNET_BN_TICKET, is not built in)
-  if (a.bn.ticket || a.bb.ticket) return false;
   if (off || a.C != 64 || a.Cout % kCOT || a.P % kTH || a.Q % 16 || a.H != a.P || a.W != a.Q) return false;
   if (a.R != 3 || a.S != 3 || a.stride != 1 || a.pad != 1 || a.x2 || a.ysplit || a.fold_on) return false;
   if (a.xform && (flip || !a.xh || a.ldxh % 8)) return false;

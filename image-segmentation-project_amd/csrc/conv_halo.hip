@@ -393,8 +393,7 @@ __device__ __forceinline__ void load_epi_constants(const ConvFwdArgs& a, float* 
 }
 
 // Block reduction of the BN sums (16 pixel lanes, then the NW waves through
-// LDS at `scratch`), fp64 atomics into replica blockIdx.x % kStatRep, and the
-// optional last-block finalisation.
+// LDS at `scratch`) and fp64 atomics into replica blockIdx.x % kStatRep.
 template <int FN, int NW, bool TWO>
 __device__ __forceinline__ void stats_atomics(const ConvFwdArgs& a, float (&q0)[FN][4], float (&q1)[FN][4],
                                               float (&q2)[FN][4], int co0, char* scratch) {
@@ -443,30 +442,6 @@ __device__ __forceinline__ void stats_atomics(const ConvFwdArgs& a, float (&q0)[
   }
 }
 
-// the launch's last block (ticket) finalises the BN (forward or backward) whose
-// sums the blocks added (stats_atomics)
-template <int COT, int NW>
-__device__ __forceinline__ void stats_ticket(const ConvFwdArgs& a, char* scratch) {
-  const BnBwdArgs& bb = a.bb;
-  const bool fbwd = bb.sums != nullptr;
-  const int tid = threadIdx.x;
-  unsigned* ticket = fbwd ? bb.ticket : a.bn.ticket;
-  if (ticket) {
-    int* flag = reinterpret_cast<int*>(scratch + NW * COT * 3 * sizeof(float));
-    if (last_block_arrive(ticket, gridDim.x * gridDim.y * gridDim.z, flag, tid < COT)) {
-      if (fbwd) bn_bwd_finalize(bb);
-      else bn_finalize(a.bn);
-    }
-  }
-}
-
-template <int FN, int NW, bool TWO>
-__device__ __forceinline__ void commit_stats(const ConvFwdArgs& a, float (&q0)[FN][4], float (&q1)[FN][4],
-                                             float (&q2)[FN][4], int co0, char* scratch) {
-  stats_atomics<FN, NW, TWO>(a, q0, q1, q2, co0, scratch);
-  stats_ticket<FN * 16, NW>(a, scratch);
-}
-
 // ---------------------------------------------------------------------------
 // weight-stationary (C = 32 * NP <= 96)
 // ---------------------------------------------------------------------------
@@ -512,7 +487,7 @@ __global__ void __launch_bounds__(NW * 64) conv3x3_ws_kernel(ConvFwdArgs a, int 
       float m, is, var;
       bn_scale_shift(a.xbn, c, xss[c], xss[NP * 32 + c], m, is, var);
     }
-    if (blockIdx.x == 0) bn_finalize(a.xbn);  // saved mean / invstd, running statistics
+    if (blockIdx.x == 0) bn_finalize(a.xbn, 0, a.xbn.C);  // saved mean / invstd, running statistics
   }
   float q0[FN][4], q1[FN][4], q2[FN][4];
 #pragma unroll
@@ -664,7 +639,7 @@ __global__ void __launch_bounds__(NW * 64) conv3x3_ws_kernel(ConvFwdArgs a, int 
     if (UNET_ABL >= 3 ? k < 3 : k < 9) TSTAMP(a.tim, UNET_ABL >= 3 ? 6 + 5 * k : 3 + 2 * k);
   }
   TSTAMP(a.tim, 20);
-  if (a.stats || a.bb.sums) commit_stats<FN, NW, false>(a, q0, q1, q2, co0, smem);
+  if (a.stats || a.bb.sums) stats_atomics<FN, NW, false>(a, q0, q1, q2, co0, smem);
   TSTAMP(a.tim, 21);
   TSTAMP_RT(a.tim, 31);
 }
@@ -811,7 +786,6 @@ __global__ void __launch_bounds__(NW * 64) conv3x3_hs_kernel(ConvFwdArgs a, int 
     tile = next;
     if (!MT || tile >= ntiles) break;
   }
-  if (stats) stats_ticket<COT, NW>(a, smem);
   TSTAMP(a.tim, 22);
   TSTAMP_RT(a.tim, 31);
 }
@@ -990,7 +964,7 @@ __global__ void __launch_bounds__(NW * 64) conv3x3s2_dgrad_kernel(ConvFwdArgs a,
     epi.fetch(a, pix, co0, lane);
     epi.store(a, ac, pix, co0, lane, cst, q0, q1, q2);
   }
-  if (a.bb.sums) commit_stats<FN, NW, false>(a, q0, q1, q2, co0, smem);
+  if (a.bb.sums) stats_atomics<FN, NW, false>(a, q0, q1, q2, co0, smem);
 }
 
 template <int FN, int RW, int NW, bool EXT>
@@ -1000,7 +974,7 @@ static hipError_t launch_s2d(const ConvFwdArgs& a, hipStream_t st) {
   constexpr size_t stage = (size_t)HPR * 64 + 9 * COT * 64 + (EXT ? (size_t)TI * 16 * 64 + COT * 64 : 0);
   constexpr size_t lds = 2 * stage + kEpiConsts * COT * sizeof(float);
   static_assert(lds <= 163840, "LDS");
-  static_assert((size_t)NW * COT * 3 * sizeof(float) + sizeof(int) <= 2 * stage, "stats scratch");
+  static_assert((size_t)NW * COT * 3 * sizeof(float) <= 2 * stage, "stats scratch");
   const int ncb = a.Cout / COT;
   const int ntiles = a.N * (a.H / TI) * (a.W / 16);
   char tag[96];

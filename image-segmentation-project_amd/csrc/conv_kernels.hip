@@ -257,7 +257,7 @@ conv_fwd_kernel(ConvFwdArgs a) {
 // sum dZ*xhat2]) are accumulated from the stored bf16 dZ, exactly what
 // bn_bwd_reduce_kernel would read back.  Either way the block's partials are
 // folded over its 16 pixel lanes and WM waves, added into replica
-// blockIdx.x % kStatRep, and the last block finalises the BN.
+// blockIdx.x % kStatRep.
 template <int MODE, int BN, int WM, int WN, int FM, int FN>
 __device__ __forceinline__ void conv_epilogue(const ConvFwdArgs& a, f32x4 (&acc)[FN][FM], char* smem, int m0,
                                               int n0, int Mtot, int py, int px_) {
@@ -438,15 +438,6 @@ __device__ __forceinline__ void conv_epilogue(const ConvFwdArgs& a, f32x4 (&acc)
         atomicAdd(dst + co, (double)s0);
         atomicAdd(dst + a.Cout + co, (double)s1);
         if (two) atomicAdd(bb.sums2 + rep + a.Cout + co, (double)s2);
-      }
-    }
-    unsigned* ticket = fbwd ? bb.ticket : a.bn.ticket;
-    if (ticket) {
-      const unsigned total = gridDim.x * gridDim.y * gridDim.z;
-      int* flag = reinterpret_cast<int*>(smem + WM * BN * 3 * sizeof(float));
-      if (last_block_arrive(ticket, total, flag, tid < BN)) {
-        if (fbwd) bn_bwd_finalize(bb);
-        else bn_finalize(a.bn);
       }
     }
   }
@@ -689,7 +680,7 @@ conv_glds_kernel(ConvFwdArgs a) {
   if constexpr (DS) {
     ConvFwdArgs d = a;  // the downsample's epilogue: its output and BN sums, no bias
     d.y = a.yds; d.ldy = a.ldyds;
-    d.stats = a.stats_ds; d.bn = a.bnds;
+    d.stats = a.stats_ds;
     d.bias = nullptr; d.add = nullptr; d.fold_on = 0;
     __syncthreads();  // the first epilogue's LDS reduction is read
     conv_epilogue<MODE, BN, WM, WN, FM, FN>(d, acc2, smem, m0, n0, Mtot, py, px_);
@@ -1908,7 +1899,7 @@ __global__ void __launch_bounds__(256) wgrad_slab_reduce_kernel(const f32x4* __r
 // converted to a bf16 LDS patch, and each thread builds its pixel's im2col row
 // (49 taps padded to K = 64) in LDS.  Forward: D[co][px] = W[co][k] .
 // im2col[px][k]; the BN batch sums are kept in registers over all the block's
-// rows and committed once (replica atomics + last-block finalise).  Weight
+// rows and committed once (replica atomics).  Weight
 // gradient: D[co][k] += sum_px dY[px][co] . im2col[px][k], both tiles
 // pixel-major and read through ds_read_b64_tr_b16; one fp32-atomic 64x64
 // partial per block.
@@ -2084,10 +2075,6 @@ __global__ void __launch_bounds__(256, 2) stem_fwd_kernel(ConvFwdArgs a, int row
     double* rep = a.stats + (size_t)(blockIdx.x % kStatRep) * 2 * a.Cout + cg;
     atomicAdd(rep + tid, (double)s0);
     atomicAdd(rep + a.Cout + tid, (double)s1);
-  }
-  if (a.bn.ticket) {
-    int* flag = reinterpret_cast<int*>(smem + 4 * 64 * 2 * sizeof(float));
-    if (last_block_arrive(a.bn.ticket, gridDim.x * gridDim.y, flag, tid < 64)) bn_finalize(a.bn);
   }
 }
 
@@ -2299,7 +2286,7 @@ static hipError_t launch_fwd_cfg(const ConvFwdArgs& a0, int classes, hipStream_t
   a.mblocks = (M + BM - 1) / BM;
   const size_t lds = 2 * (size_t)(BM + BN) * BK * 2;
   size_t need = lds;
-  const size_t red = (size_t)WM * BN * 3 * sizeof(float) + 16;
+  const size_t red = (size_t)WM * BN * 3 * sizeof(float);
   if (red > need) need = red;
   dim3 grid(a.mblocks * a.nblocks, 1, classes);
   set_kernel_tag("conv_fwd_kernel<%d, %d, %d, %d, %d, %d, %d>", MODE, ALOAD, BM, BN, BK, WM, WN);
@@ -2326,7 +2313,7 @@ static hipError_t launch_glds_cfg(const ConvFwdArgs& a0, int classes, hipStream_
   if (DS) stages = NS;  // the downsample tile sits behind all NS stages
   size_t lds = (size_t)stages * (BM + B_ROWS) * ROWB;
   if (DS) lds += (size_t)(a.C / BK) * B_ROWS * ROWB;
-  const size_t red = (size_t)WM * BN * 3 * sizeof(float) + 16;
+  const size_t red = (size_t)WM * BN * 3 * sizeof(float);
   if (red > lds) lds = red;
   dim3 grid(a.mblocks * a.nblocks, 1, classes);
   set_kernel_tag(DS ? "conv_glds_kernel<%d, %d, %d, %d, %d, %d, %d> +ds" : "conv_glds_kernel<%d, %d, %d, %d, %d, %d, %d>",
@@ -2458,7 +2445,7 @@ static hipError_t launch_f8_cfg(const ConvFwdArgs& a0, hipStream_t st) {
   constexpr int NW = WM * WN, RPI = 8;
   constexpr size_t B_ROWS = ((BN + RPI * NW - 1) / (RPI * NW)) * RPI * NW;
   size_t lds = (size_t)NS * (BM + B_ROWS) * 128;
-  const size_t red = (size_t)WM * BN * 3 * sizeof(float) + 16;
+  const size_t red = (size_t)WM * BN * 3 * sizeof(float);
   if (red > lds) lds = red;
   set_kernel_tag("conv_f8_kernel<%d, %d, %d, %d, %d>", BM, BN, NS, WM, WN);
   hipLaunchKernelGGL((conv_f8_kernel<BM, BN, NS, WM, WN>), dim3(a.mblocks * a.nblocks), dim3(NW * 64), lds, st, a);

@@ -67,8 +67,7 @@ __global__ void __launch_bounds__(kCtWaves * 64) convt2x2_kernel(ConvFwdArgs a, 
   float* cst = reinterpret_cast<float*>(smem + NN * KB);  // MODE 0: bias [Co]; MODE 1: mean | invstd [2][NN]
   float* red = cst + 2 * NN;                               // [kCtWaves][NN][2], then bias sums [kCtWaves][Co]
   float* redb = red + kCtWaves * NN * 2;
-  int* flag = reinterpret_cast<int*>(redb + kCtWaves * Co);
-  float* xss = reinterpret_cast<float*>(flag + 4);  // MODE 0 xform: [2][K] scale | shift
+  float* xss = redb + kCtWaves * Co;                       // MODE 0 xform: [2][K] scale | shift
   const bool xf = MODE == 0 && a.xform != 0;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int pl = lane & 15, kq = lane >> 4;
@@ -137,7 +136,7 @@ __global__ void __launch_bounds__(kCtWaves * 64) convt2x2_kernel(ConvFwdArgs a, 
         float m, is, var;
         bn_scale_shift(a.xbn, c, xss[c], xss[K + c], m, is, var);
       }
-      if (blockIdx.x == 0) bn_finalize(a.xbn);  // saved mean / invstd, running statistics
+      if (blockIdx.x == 0) bn_finalize(a.xbn, 0, a.xbn.C);  // saved mean / invstd, running statistics
     }
   } else if constexpr (FB) {
     for (int c = tid; c < NN; c += kCtWaves * 64) {
@@ -328,9 +327,6 @@ __global__ void __launch_bounds__(kCtWaves * 64) convt2x2_kernel(ConvFwdArgs a, 
       atomicAdd(a.bias_acc + (size_t)rep * Co + c, (double)s);
     }
   }
-  if constexpr (FB) {
-    if (a.bb.ticket && last_block_arrive(a.bb.ticket, gridDim.x, flag, true)) bn_bwd_finalize(a.bb);
-  }
 }
 
 template <int MODE, int NT, int KS, int MT, bool FB>
@@ -339,7 +335,7 @@ static hipError_t convt_cfg(const ConvFwdArgs& a, hipStream_t st) {
   const long long M = (long long)a.N * a.H * a.W;
   if (M % (16 * MT)) return hipErrorNotSupported;
   const int ngroups = (int)(M / (16 * MT));
-  const size_t lds = (size_t)NN * K * 2 + 2 * NN * 4 + kCtWaves * NN * 2 * 4 + kCtWaves * Co * 4 + 16 +
+  const size_t lds = (size_t)NN * K * 2 + 2 * NN * 4 + kCtWaves * NN * 2 * 4 + kCtWaves * Co * 4 +
                      (MODE == 0 && a.xform ? 2 * K * 4 : 0);
   // the fused form keeps one block per CU: its per-block reduction and fp64
   // atomics amortise over more groups (micro: upconv1 38.6 -> 34.8 us,
@@ -380,7 +376,7 @@ hipError_t launch_convt2x2(const ConvFwdArgs& a, int mode, hipStream_t st) {
   if (mode != 0 && mode != 1) return hipErrorInvalidValue;
   if (a.add || a.stats || a.x2 || a.ysplit || a.fold_on || a.bb.y2 || a.wch) return hipErrorNotSupported;
   if (a.xform) {  // forward only, every operand of the fold in place (no fallback takes it)
-    if (mode != 0 || !convt2x2_xform_ok(a) || !al16(a.xh) || !a.xbn.stats || a.xbn.C != a.C || a.xbn.ss)
+    if (mode != 0 || !convt2x2_xform_ok(a) || !al16(a.xh) || !a.xbn.stats || a.xbn.C != a.C)
       return hipErrorInvalidValue;
   }
   if (mode == 0 && (a.bb.sums || a.bias_acc)) return hipErrorInvalidValue;
@@ -412,7 +408,7 @@ hipError_t launch_convt2x2(const ConvFwdArgs& a, int mode, hipStream_t st) {
 // implicit-GEMM tiles ran them at 1.5-2.5 TB/s.
 //   MODE 0 forward:        Y[m][co] = bias[co] + sum_ci W[co][ci] X[m][ci];
 //                          stats != null: BN sums of the fp32 values
-//                          (conv_epilogue's), last block finalises with a ticket
+//                          (conv_epilogue's)
 //   MODE 1 data gradient:  dX[m][ci] = sum_co W[co][ci] dY[m][co] (+ add[m][ci])
 // Both read their pack ([Cout][Ci] forward, [Ci][Cout] dgrad) as [NN][K] rows.
 // ---------------------------------------------------------------------------
@@ -423,7 +419,6 @@ __global__ void __launch_bounds__(kCtWaves * 64) conv1x1_kernel(ConvFwdArgs a, i
   char* wl = smem;                                         // [NN][K] bf16
   float* cst = reinterpret_cast<float*>(smem + NN * KB);  // bias [NN]
   float* red = cst + NN;                                   // [kCtWaves][NN][2]
-  int* flag = reinterpret_cast<int*>(red + kCtWaves * NN * 2);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int pl = lane & 15, kq = lane >> 4;
   const bool stats = a.stats != nullptr, add = a.add != nullptr;
@@ -524,7 +519,6 @@ __global__ void __launch_bounds__(kCtWaves * 64) conv1x1_kernel(ConvFwdArgs a, i
     atomicAdd(a.stats + rep + c, (double)s0);
     atomicAdd(a.stats + rep + NN + c, (double)s1);
   }
-  if (a.bn.ticket && last_block_arrive(a.bn.ticket, gridDim.x, flag, true)) bn_finalize(a.bn);
 }
 
 template <int NT, int KS>
@@ -533,7 +527,7 @@ static hipError_t conv1x1_cfg(const ConvFwdArgs& a, hipStream_t st) {
   const long long M = (long long)a.N * a.H * a.W;
   if (M % 16) return hipErrorNotSupported;
   const int ngroups = (int)(M / 16);
-  const size_t lds = (size_t)NN * K * 2 + NN * 4 + kCtWaves * NN * 2 * 4 + 16;
+  const size_t lds = (size_t)NN * K * 2 + NN * 4 + kCtWaves * NN * 2 * 4;
   // with statistics two blocks per CU instead of four: the per-block
   // reduction and its atomics amortise over more groups
   const int per_cu = a.stats ? 2 : 4;

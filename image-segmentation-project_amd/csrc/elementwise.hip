@@ -35,22 +35,6 @@ static inline int grid_for(int64_t work, int per_block, int cap = 2048) {
 // statistics: save_mean/save_invstd for the backward and the running stats
 // (momentum 0.1, unbiased variance), matching torch.nn.BatchNorm2d training.
 // ---------------------------------------------------------------------------
-__device__ void bn_finalize_block0(const BnLaunch& p, int tid, int nthreads, int cbeg, int cend) {
-  for (int c = cbeg + tid; c < cend; c += nthreads) {
-    float sc, sh, m, inv, var;
-    bn_scale_shift(p, c, sc, sh, m, inv, var);
-    if (p.training) {
-      p.save_mean[c] = m;
-      p.save_invstd[c] = inv;
-      const double n = p.count;
-      const float unb = (float)((double)var * (n / (n > 1.0 ? n - 1.0 : 1.0)));
-      p.run_mean[c] = (1.f - p.momentum) * p.run_mean[c] + p.momentum * m;
-      p.run_var[c] = (1.f - p.momentum) * p.run_var[c] + p.momentum * unb;
-      if (c == 0 && p.nbt) *p.nbt += 1;  // exactly once per training forward, like the running stats
-    }
-  }
-}
-
 // Thread layout of the per-channel BN kernels: a block covers one group of
 // CG channels (blockIdx.y; CG = 64 when C % 64 == 0, else C) so its
 // coefficient prologue reads CG channels' replica sums, not C; inside the
@@ -93,19 +77,12 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(BnApplyArgs a) {
   for (int c = threadIdx.x; c < CG; c += blockDim.x) {
     const int ch = cg0 + c;
     float m, inv, var;
-    if (a.bn.training && a.bn.ss) {  // finalised by the producing conv's last block
-      coef[c] = a.bn.ss[ch];
-      coef[CG + c] = a.bn.ss[a.C + ch];
-    } else {
-      bn_scale_shift(a.bn, ch, coef[c], coef[CG + c], m, inv, var);
-    }
-    if (RES == 2) {
-      if (a.bn2.training && a.bn2.ss) {
-        coef[2 * CG + c] = a.bn2.ss[ch];
-        coef[3 * CG + c] = a.bn2.ss[a.C + ch];
-      } else {
-        bn_scale_shift(a.bn2, ch, coef[2 * CG + c], coef[3 * CG + c], m, inv, var);
-      }
+    bn_scale_shift(a.bn, ch, coef[c], coef[CG + c], m, inv, var);
+  }
+  if constexpr (RES == 2) {  // a loop of its own: the two replica sums are not interleaved (VGPRs)
+    for (int c = threadIdx.x; c < CG; c += blockDim.x) {
+      float m, inv, var;
+      bn_scale_shift(a.bn2, cg0 + c, coef[2 * CG + c], coef[3 * CG + c], m, inv, var);
     }
   }
   __syncthreads();
@@ -156,11 +133,10 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(BnApplyArgs a) {
       }
     }
   }
-  // standalone use (no producer finalised the stats): block (0, g) finalises
-  // its channel group
+  // block (0, g) finalises its channel group
   if (blockIdx.x == 0) {
-    if (!a.bn.ss) bn_finalize_block0(a.bn, threadIdx.x, blockDim.x, cg0, cg0 + CG);
-    if (RES == 2 && !a.bn2.ss) bn_finalize_block0(a.bn2, threadIdx.x, blockDim.x, cg0, cg0 + CG);
+    bn_finalize(a.bn, cg0, cg0 + CG);
+    if (RES == 2) bn_finalize(a.bn2, cg0, cg0 + CG);
   }
 }
 
@@ -282,7 +258,6 @@ __global__ void __launch_bounds__(256) bn_bwd_reduce_kernel(BnBwdArgs a) {
     }
     __syncthreads();
   }
-  if (a.ticket && last_block_arrive(a.ticket, gridDim.x, reinterpret_cast<int*>(red), true)) bn_bwd_finalize(a);
 }
 
 hipError_t launch_bn_bwd_reduce(const BnBwdArgs& a, hipStream_t st) {
@@ -345,41 +320,31 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(BnBwdArgs a, double i
   if (row < rows) load(base);  // first pass in flight during the prologue
   for (int c = threadIdx.x; c < CG; c += blockDim.x) {
     const int ch = cg0 + c;
-    float k1, m1, m2, k1b = 0.f, m2b = 0.f;
-    if (a.coef) {  // finalised by the reduce's (or fused producer's) last block
-      k1 = a.coef[ch];
-      m1 = a.coef[a.C + ch];
-      m2 = a.coef[2 * a.C + ch];
-      if (TWO) { k1b = a.coef[3 * a.C + ch]; m2b = a.coef[4 * a.C + ch]; }
-    } else {
-      double s1, s2, t2 = 0.0;
-      float cA, cB, cC;
-      bn_bwd_apply_coef(a, ch, inv_n, cA, cB, cC, s1, s2);
-      if (TWO) {
-        for (int r = 0; r < kStatRep; ++r) t2 += a.sums2[(size_t)r * 2 * a.C + a.C + ch];
-        k1b = __fmul_rn(a.gamma2[ch], a.invstd2[ch]);
-        m2b = (float)__dmul_rn(t2, inv_n);
-      }
-      if (bx == 0) {
-        a.dgamma[ch] = (float)s2;
-        a.dbeta[ch] = (float)s1;
-        if (TWO) {
-          a.dgamma2[ch] = (float)t2;
-          a.dbeta2[ch] = (float)s1;  // same dZ feeds both BNs
-        }
-      }
-      coef[c] = cA;
-      coef[CG + c] = cB;
-      coef[2 * CG + c] = cC;
-      m1 = (float)__dmul_rn(s1, inv_n);
-      if (TWO) {
-        const float isb = a.invstd2[ch], mub = a.mean2[ch];
-        bn_bwd_coef_abc(k1b, m1, m2b, isb, mub, coef[3 * CG + c], coef[4 * CG + c], coef[5 * CG + c]);
-      }
-      continue;
+    float k1b = 0.f, m2b = 0.f;
+    double s1, s2, t2 = 0.0;
+    float cA, cB, cC;
+    bn_bwd_apply_coef(a, ch, inv_n, cA, cB, cC, s1, s2);
+    if (TWO) {
+      for (int r = 0; r < kStatRep; ++r) t2 += a.sums2[(size_t)r * 2 * a.C + a.C + ch];
+      k1b = __fmul_rn(a.gamma2[ch], a.invstd2[ch]);
+      m2b = (float)__dmul_rn(t2, inv_n);
     }
-    bn_bwd_coef_abc(k1, m1, m2, a.invstd[ch], a.mean[ch], coef[c], coef[CG + c], coef[2 * CG + c]);
-    if (TWO) bn_bwd_coef_abc(k1b, m1, m2b, a.invstd2[ch], a.mean2[ch], coef[3 * CG + c], coef[4 * CG + c], coef[5 * CG + c]);
+    if (bx == 0) {
+      a.dgamma[ch] = (float)s2;
+      a.dbeta[ch] = (float)s1;
+      if (TWO) {
+        a.dgamma2[ch] = (float)t2;
+        a.dbeta2[ch] = (float)s1;  // same dZ feeds both BNs
+      }
+    }
+    coef[c] = cA;
+    coef[CG + c] = cB;
+    coef[2 * CG + c] = cC;
+    const float m1 = (float)__dmul_rn(s1, inv_n);
+    if (TWO) {
+      const float isb = a.invstd2[ch], mub = a.mean2[ch];
+      bn_bwd_coef_abc(k1b, m1, m2b, isb, mub, coef[3 * CG + c], coef[4 * CG + c], coef[5 * CG + c]);
+    }
   }
   __syncthreads();
   float cA[8], cB[8], cC[8], dA[TWO ? 8 : 1], dB[TWO ? 8 : 1], dC[TWO ? 8 : 1];
@@ -617,7 +582,6 @@ __global__ void __launch_bounds__(256) maxpool_bwd_kernel(MaxPoolArgs a, int rpb
   if (!fz) return;
   // fold the block's per-thread channel sums (thread t holds chunk t % CC)
   __shared__ float red[256 * 8];
-  __shared__ int flag;
   for (int q = 0; q < 2; ++q) {
     const float* src = q == 0 ? s1 : s2;
 #pragma unroll
@@ -632,7 +596,6 @@ __global__ void __launch_bounds__(256) maxpool_bwd_kernel(MaxPoolArgs a, int rpb
     }
     __syncthreads();
   }
-  if (bb.ticket && last_block_arrive(bb.ticket, gridDim.x, &flag, (int)threadIdx.x < a.C)) bn_bwd_finalize(bb);
 }
 
 // Stem forward tail in one pass: act = relu(bn(x)) (x = raw 7x7 conv output)
@@ -650,8 +613,7 @@ __global__ void __launch_bounds__(256) bn_relu_maxpool_fwd_kernel(MaxPoolArgs a,
   __shared__ float coef[2][256];
   for (int c = threadIdx.x; c < a.C; c += blockDim.x) {
     float m, inv, var;
-    if (a.bn.training && a.bn.ss) { coef[0][c] = a.bn.ss[c]; coef[1][c] = a.bn.ss[a.C + c]; }
-    else bn_scale_shift(a.bn, c, coef[0][c], coef[1][c], m, inv, var);
+    bn_scale_shift(a.bn, c, coef[0][c], coef[1][c], m, inv, var);
   }
   __syncthreads();
   float sc[8], sh[8];
@@ -717,7 +679,7 @@ __global__ void __launch_bounds__(256) bn_relu_maxpool_fwd_kernel(MaxPoolArgs a,
     }
   }
   // batch statistics of the BN (save_mean/invstd, running stats): block 0
-  if (blockIdx.x == 0 && !a.bn.ss) bn_finalize_block0(a.bn, threadIdx.x, blockDim.x, 0, a.C);
+  if (blockIdx.x == 0) bn_finalize(a.bn, 0, a.C);
 }
 
 static inline int rows_per_block(int nrows, int target_blocks) {
@@ -787,8 +749,7 @@ constexpr int kHeadHP = 4;  // pixels in flight per thread (Cin = 32: 16 x 16 B 
 // head reads the raw conv output y and forms act = bf16(relu(y * sc + sh)),
 // the value bn_apply_kernel would have stored, in both passes (fmaf: the same
 // bits in the forward and the backward).  sc / sh per channel into LDS as
-// bn_apply_kernel computes them (the producer's finalised ss, or the replica
-// sums).
+// bn_apply_kernel computes them (from the replica sums).
 __device__ __forceinline__ float head_act(float y, float sc, float sh) {
   const float v = fmaf(y, sc, sh);
   return bf2f(f2bf(v > 0.f ? v : 0.f));
@@ -796,12 +757,7 @@ __device__ __forceinline__ float head_act(float y, float sc, float sh) {
 __device__ void head_bn_coef(const HeadArgs& a, float2* ss) {
   for (int c = threadIdx.x; c < a.Cin; c += blockDim.x) {
     float sc, sh, m, inv, var;
-    if (a.bn.training && a.bn.ss) {
-      sc = a.bn.ss[c];
-      sh = a.bn.ss[a.Cin + c];
-    } else {
-      bn_scale_shift(a.bn, c, sc, sh, m, inv, var);
-    }
+    bn_scale_shift(a.bn, c, sc, sh, m, inv, var);
     ss[c] = make_float2(sc, sh);
   }
 }
@@ -858,7 +814,7 @@ __global__ void __launch_bounds__(256) head_fwd_kernel(HeadArgs a) {
   }
   // the folded BN's statistics: save_mean / save_invstd and the running stats
   // (bn_apply_kernel's block 0 in the unfolded path)
-  if (fold && blockIdx.x == 0 && !a.bn.ss) bn_finalize_block0(a.bn, threadIdx.x, blockDim.x, 0, a.Cin);
+  if (fold && blockIdx.x == 0) bn_finalize(a.bn, 0, a.Cin);
 }
 
 // thread = (8-channel chunk, pixel row); U[c][ab] partials live in registers;
@@ -932,7 +888,13 @@ __global__ void __launch_bounds__(256) head_bwd_kernel(HeadArgs a) {
       }
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        g[k] = d[0] * Vl[k][0] + d[1] * Vl[k][1] + d[2] * Vl[k][2] + d[3] * Vl[k][3];
+        // explicit FMAs in a fixed association: left to the compiler's
+        // contraction, the rounding depended on how it paired channels into
+        // packed FMAs (channels with k & 2 started from d1 V1), which changed
+        // with unrelated code after the loop.  This is the association the
+        // library has always been built with.
+        const float t = (k & 2) ? fmaf(d[0], Vl[k][0], d[1] * Vl[k][1]) : fmaf(d[1], Vl[k][1], d[0] * Vl[k][0]);
+        g[k] = fmaf(d[3], Vl[k][3], fmaf(d[2], Vl[k][2], t));
 #pragma unroll
         for (int ab = 0; ab < 4; ++ab) U[k][ab] += x[k] * d[ab];
       }
@@ -976,10 +938,6 @@ __global__ void __launch_bounds__(256) head_bwd_kernel(HeadArgs a) {
       const int q = (t - LU) / CIN, c = (t - LU) - q * CIN;
       atomicAdd(bb.sums + (size_t)(blockIdx.x % kStatRep) * 2 * CIN + q * CIN + c, (double)v);
     }
-  }
-  if (fz && bb.ticket) {
-    __shared__ int flag;
-    if (last_block_arrive(bb.ticket, gridDim.x, &flag, true)) bn_bwd_finalize(bb);
   }
 }
 
@@ -1159,7 +1117,7 @@ __global__ void __launch_bounds__(256) head_fwd_mc_kernel(HeadArgs a) {
       }
     }
   }
-  if (fold && blockIdx.x == 0 && !a.bn.ss) bn_finalize_block0(a.bn, threadIdx.x, blockDim.x, 0, a.Cin);
+  if (fold && blockIdx.x == 0) bn_finalize(a.bn, 0, a.Cin);
 }
 
 // sum over the lanes that hold the same 8-channel chunk (lane % CC) of a wave
@@ -1386,10 +1344,6 @@ __global__ void __launch_bounds__(256) head_bwd_dx_mc_kernel(HeadArgs a) {
       const float v = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
       atomicAdd(bb.sums + (size_t)(blockIdx.x % kStatRep) * 2 * CIN + t, (double)v);
     }
-    if (bb.ticket) {
-      __shared__ int flag;
-      if (last_block_arrive(bb.ticket, gridDim.x, &flag, true)) bn_bwd_finalize(bb);
-    }
   }
 }
 
@@ -1477,7 +1431,7 @@ hipError_t launch_head_bwd(const HeadArgs& a, hipStream_t st) {
   if (a.bn_fold && (!a.bb.sums || a.bb.y != a.x || a.bb.ldy != a.ldx || a.bn.C != a.Cin || !a.bn.stats))
     return hipErrorInvalidValue;
   if (a.K > 1) {
-    // U passes first, a chunk of classes each, then dX (its last block finalises the fused BN sums)
+    // U passes first, a chunk of classes each, then dX (which adds the fused BN sums)
     const int g = grid_for(total, rows * kHeadBwdHP * 4, 512);
     for (int k0 = 0; k0 < a.K; k0 += kHeadBwdKC) {
       if (a.Cin == 32) hipLaunchKernelGGL(head_bwd_u_mc_kernel<32>, dim3(g), dim3(256), 0, st, a, k0);

@@ -57,8 +57,6 @@ struct Bn {
   int idx;                // BN ordinal (buffers 3*idx + 0/1)
   int C;
   size_t stats, bsums, save;  // ws offsets: fp64 [R][2C] fwd, fp64 [R][2C] bwd, fp32 mean|invstd
-  size_t ss, coef;            // fp32 scale|shift [2C], backward coefficients [5C]
-  size_t tfwd, tbwd;          // last-block tickets (zeroed with the fwd / bwd sums)
 };
 
 enum { L_CONV = 0, L_CONVT = 1, L_STEM = 2 };
@@ -171,8 +169,6 @@ struct unet_plan {
   // removed.  Two split-K slabs alternate so a deferred
   // reduction never reads partials the next weight gradient overwrites.
   int slab_next = 0;
-  std::vector<hipEvent_t> syncpool;
-  int syncused = 0;
   bool want_events = false;  // DDP overlap: record one hipEvent per gradient bucket
   // in-kernel phase timing (debug build only, unet_timing_enable): one slot of
   // kTimBlocks x kTimSlots stamps per conv launch, in launch order
@@ -182,11 +178,6 @@ struct unet_plan {
   std::vector<std::string> tim_names;
   // BN-backward reductions fused into the producing conv dgrad (UNET_NO_BWD_FUSE=1: off, A/B only)
   bool fuse_bwd = std::getenv("UNET_NO_BWD_FUSE") == nullptr;
-  // BN coefficients recomputed by every consumer block from the replica sums
-  // (default; measured 0.28 ms/step faster) vs finalised by the producing
-  // kernel's last block, whose blocks must then drain their atomics and take a
-  // ticket before exiting (UNET_BN_TICKET=1)
-  bool bn_ticket = std::getenv("UNET_BN_TICKET") && std::getenv("UNET_BN_TICKET")[0] == '1';
   // eval forward: BN folded into the conv epilogues (UNET_NO_EVAL_FOLD=1: separate BN passes, A/B only)
   bool eval_fold = std::getenv("UNET_NO_EVAL_FOLD") == nullptr;
   // stem BN-backward apply fused into the stem weight gradient's dY load
@@ -485,10 +476,7 @@ static int build_plan(unet_plan* p) {
   Alloc A;
   // zeroed at forward start: BN fwd sums
   p->zero_fwd_off = A.take(0);
-  for (auto& b : p->bns) {
-    b.stats = A.take((size_t)kStatRep * 2 * b.C * sizeof(double));
-    b.tfwd = A.take(sizeof(unsigned));
-  }
+  for (auto& b : p->bns) b.stats = A.take((size_t)kStatRep * 2 * b.C * sizeof(double));
   for (int l = 0; l < (int)p->atts.size(); ++l) {
     Att& t = p->atts[l];
     t.pst = A.take(2 * sizeof(double));
@@ -498,10 +486,7 @@ static int build_plan(unet_plan* p) {
   p->zero_fwd_bytes = A.top - p->zero_fwd_off;
   // zeroed at backward start: BN bwd sums, convT bias sums, head sums, wgrad accumulators
   p->zero_bwd_off = A.take(0);
-  for (auto& b : p->bns) {
-    b.bsums = A.take((size_t)kStatRep * 2 * b.C * sizeof(double));
-    b.tbwd = A.take(sizeof(unsigned));
-  }
+  for (auto& b : p->bns) b.bsums = A.take((size_t)kStatRep * 2 * b.C * sizeof(double));
   for (auto& cv : p->convs)
     if (cv.kind == L_CONVT) cv.bias_acc = A.take((size_t)kStatRep * cv.Co * sizeof(double));
   // [kStatRep][K * (Cin*4 + 1)]
@@ -523,11 +508,7 @@ static int build_plan(unet_plan* p) {
     else n = (size_t)cv.Co * cv.Ci * cv.R * cv.S;
     cv.wacc = A.take(n * sizeof(float));
   }
-  for (auto& b : p->bns) {
-    b.save = A.take((size_t)2 * b.C * sizeof(float));
-    b.ss = A.take((size_t)2 * b.C * sizeof(float));
-    b.coef = A.take((size_t)5 * b.C * sizeof(float));
-  }
+  for (auto& b : p->bns) b.save = A.take((size_t)2 * b.C * sizeof(float));
   for (auto& cv : p->convs) {
     if (cv.kind == L_STEM) {
       cv.pk_fwd = A.take((size_t)cv.Co * 64 * 2);
@@ -869,9 +850,6 @@ static int ensure_events(unet_plan* p) {
 // ---------------------------------------------------------------------------
 // execution helpers
 // ---------------------------------------------------------------------------
-int stream_edge(unet_plan* p, hipStream_t from, hipStream_t to);
-int pooled_event(unet_plan* p, hipEvent_t* out);
-
 namespace {
 
 struct Ctx {
@@ -881,11 +859,6 @@ struct Ctx {
   float* const* buf;
   hipStream_t st;
   int training;
-  // weight-gradient and split-K reduction streams: both are st (the backward
-  // is single-stream since the two-stream variants were removed);
-  // kept as names so the launch sites say which role a launch plays
-  hipStream_t wst = nullptr;
-  hipStream_t rst = nullptr;
   bf16_t* A(const Act& a) const { return reinterpret_cast<bf16_t*>(ws + a.off); }
   template <class T> T* W(size_t off) const { return reinterpret_cast<T*>(ws + off); }
 };
@@ -905,8 +878,6 @@ BnLaunch bn_launch(const Ctx& x, int bi, int64_t npix) {
   l.eps = x.p->cfg.bn_eps;
   l.momentum = x.p->cfg.bn_momentum;
   l.training = x.training;
-  l.ss = x.p->bn_ticket ? x.W<float>(b.ss) : nullptr;
-  l.ticket = x.p->bn_ticket ? x.W<unsigned>(b.tfwd) : nullptr;
   // buffers are (running_mean, running_var, num_batches_tracked) per BN
   l.nbt = x.buf && x.training ? reinterpret_cast<long long*>(x.buf[3 * b.idx + 2]) : nullptr;
   return l;
@@ -956,7 +927,6 @@ int conv_forward(const Ctx& x, int ci, const Act& in, const Act& out, int bn_for
   a.y = x.A(out); a.ldy = out.ld;
   a.bias = cv.b >= 0 ? x.prm[cv.b] : nullptr;
   a.stats = (bn_for_stats >= 0 && x.training) ? x.W<double>(x.p->bns[bn_for_stats].stats) : nullptr;
-  if (a.stats) a.bn = bn_launch(x, bn_for_stats, (int64_t)x.p->cfg.N * out.H * out.W);
   if (fold_bn >= 0) {
     a.fold = bn_launch(x, fold_bn, (int64_t)x.p->cfg.N * out.H * out.W);
     a.fold.training = 0;
@@ -1004,7 +974,6 @@ int conv_forward(const Ctx& x, int ci, const Act& in, const Act& out, int bn_for
     b.wds = x.W<bf16_t>(x.p->convs[ds].pk_fwd);
     b.yds = x.A(*yds); b.ldyds = yds->ld;
     b.stats_ds = dsbn >= 0 ? x.W<double>(x.p->bns[dsbn].stats) : nullptr;
-    if (b.stats_ds) b.bnds = bn_launch(x, dsbn, (int64_t)x.p->cfg.N * yds->H * yds->W);
     const hipError_t e = launch_conv_fwd(b, MODE_FWD, x.st);
     if (e != hipErrorNotSupported) {
       CK(e);
@@ -1034,7 +1003,7 @@ int conv_forward(const Ctx& x, int ci, const Act& in, const Act& out, int bn_for
 // ReLU in its staging and store the activation `h` itself?
 bool xform_ok(const Ctx& x, int ci, const Act& yraw, const Act& h, const Act& out) {
   const unet_plan* p = x.p;
-  if (!x.training || !p->bn_xform || p->bn_ticket) return false;
+  if (!x.training || !p->bn_xform) return false;
   const Conv& cv = p->convs[ci];
   if (cv.f8 || cv.kind != L_CONV || h.H != yraw.H || h.W != yraw.W || h.C != yraw.C) return false;
   ConvFwdArgs a = {};
@@ -1051,7 +1020,7 @@ bool xform_ok(const Ctx& x, int ci, const Act& yraw, const Act& h, const Act& ou
 // channel-attention forward reads d.out first)
 bool up_xform_ok(const Ctx& x, int l) {
   const unet_plan* p = x.p;
-  if (!x.training || !p->bn_xform || p->bn_ticket || !p->atts.empty() || l + 1 >= (int)p->decs.size()) return false;
+  if (!x.training || !p->bn_xform || !p->atts.empty() || l + 1 >= (int)p->decs.size()) return false;
   const Dec& d = p->decs[l];
   const Dec& n = p->decs[l + 1];
   const Conv& cv = p->convs[n.up];
@@ -1150,28 +1119,28 @@ int wgrad_and_reduce(const Ctx& x, ConvWgradArgs& a, int mode, const std::string
   // a reduction deferred two wgrads ago (the one between had no split-K, and
   // no apply launch took it) still reads this slab: it runs first
   if (wgrad_deferred_reads(a.slab)) {
-    ProfScope pr(p, x.rst, "wgrad_reduce (deferred)", 0);
-    CK(launch_wgrad_flush(x.rst));
+    ProfScope pr(p, x.st, "wgrad_reduce (deferred)", 0);
+    CK(launch_wgrad_flush(x.st));
   }
   a.tim = tim_slot(p, "wgrad " + name);
   {
-    ProfScope ps(p, x.wst, "wgrad " + name, flops);
-    if (mode == 2) CK(launch_convt_wgrad(a, x.wst));
-    else CK(launch_conv_wgrad(a, mode, x.wst));
+    ProfScope ps(p, x.st, "wgrad " + name, flops);
+    if (mode == 2) CK(launch_convt_wgrad(a, x.st));
+    else CK(launch_conv_wgrad(a, mode, x.st));
   }
   if (!wgrad_pending()) return 0;
-  if (p->merge_reduce && x.rst == x.wst && x.wst == x.st) {
+  if (p->merge_reduce) {
     // one reduction at most waits for an apply launch; an older one runs now
     // (it reads the other slab, so the order against this wgrad is free)
     if (wgrad_deferred()) {
-      ProfScope pr(p, x.rst, "wgrad_reduce (deferred)", 0);
-      CK(launch_wgrad_flush(x.rst));
+      ProfScope pr(p, x.st, "wgrad_reduce (deferred)", 0);
+      CK(launch_wgrad_flush(x.st));
     }
     if (wgrad_defer()) return 0;
   }
   {
-    ProfScope pr(p, x.rst, "wgrad_reduce " + name, 0);
-    CK(launch_wgrad_finish(x.rst));
+    ProfScope pr(p, x.st, "wgrad_reduce " + name, 0);
+    CK(launch_wgrad_finish(x.st));
   }
   return 0;
 }
@@ -1271,8 +1240,8 @@ int flush_wgrad_batch(const Ctx& x) {
       fl += 2.0 * a.N * a.P * a.Q * a.Cout * a.C * 9;
     }
     {
-      ProfScope ps(p, x.wst, nm, fl);
-      CK(launch_wgrad_batch(b, x.wst));
+      ProfScope ps(p, x.st, nm, fl);
+      CK(launch_wgrad_batch(b, x.st));
     }
     first += n;
   }
@@ -1336,8 +1305,6 @@ BnBwdArgs bwd_args(const Ctx& x, int bi, const Act& dout, const Act& out, const 
     a.dbeta2 = grads + x.p->params[b2.beta].flat;
   }
   if (dres) { a.dres = x.A(*dres); a.lddres = dres->ld; }
-  a.ticket = x.p->bn_ticket ? x.W<unsigned>(b.tbwd) : nullptr;
-  a.coef = x.p->bn_ticket ? x.W<float>(b.coef) : nullptr;
   a.npix = (int64_t)x.p->cfg.N * y.H * y.W; a.C = y.C; a.relu = 1;
   return a;
 }
@@ -1353,7 +1320,7 @@ int bn_backward(const Ctx& x, int bi, BnBwdArgs a, bool fused) {
     CK(launch_bn_bwd_reduce(a, x.st));
   }
   ReduceTail r;
-  if (wgrad_deferred() && x.wst == x.st && wgrad_take_deferred(&r)) {
+  if (wgrad_deferred() && wgrad_take_deferred(&r)) {
     const hipError_t e = launch_bn_bwd_apply_reduce(a, r, x.st);
     if (e == hipSuccess) return 0;
     if (e != hipErrorNotSupported) CK(e);
@@ -1370,16 +1337,15 @@ int bn_backward(const Ctx& x, int bi, BnBwdArgs a, bool fused) {
 // the backward)
 int flush_reduce(const Ctx& x) {
   if (!wgrad_deferred()) return 0;
-  ProfScope pr(x.p, x.wst, "wgrad_reduce (deferred)", 0);
-  CK(launch_wgrad_flush(x.wst));
+  ProfScope pr(x.p, x.st, "wgrad_reduce (deferred)", 0);
+  CK(launch_wgrad_flush(x.st));
   return 0;
 }
 
 int unpack_bucket(const Ctx& x, int bk, float* grads) {
   RUN(flush_wgrad_batch(x));
   RUN(flush_reduce(x));
-  if (x.rst != x.wst) RUN(stream_edge(x.p, x.rst, x.wst));  // every reduction so far is in dW
-  ProfScope ps(x.p, x.wst, "unpack", 0);
+  ProfScope ps(x.p, x.st, "unpack", 0);
   UnpackTable local;
   local.n = 0;
   // no bucket events: nothing waits for this bucket before the backward ends,
@@ -1393,7 +1359,7 @@ int unpack_bucket(const Ctx& x, int bk, float* grads) {
     auto zero = [&](int param) -> int {
       t.e[t.n++] = UnpackEntry{nullptr, grads + x.p->params[param].flat, UP_ZERO,
                                (int)x.p->params[param].numel, 1, 1, 1};
-      if (t.n == kMaxPack) { CK(launch_unpack(t, x.wst)); t.n = 0; }
+      if (t.n == kMaxPack) { CK(launch_unpack(t, x.st)); t.n = 0; }
       return 0;
     };
     for (const Dec& d : x.p->decs) {
@@ -1411,7 +1377,7 @@ int unpack_bucket(const Ctx& x, int bk, float* grads) {
       const Conv& up = x.p->convs[d.up];
       t.e[t.n++] = UnpackEntry{reinterpret_cast<const float*>(x.W<double>(up.bias_acc)),
                                grads + x.p->params[up.b].flat, UP_D2F, up.Co, 1, 1, 1};
-      if (t.n == kMaxPack) { CK(launch_unpack(t, x.wst)); t.n = 0; }
+      if (t.n == kMaxPack) { CK(launch_unpack(t, x.st)); t.n = 0; }
     }
   }
   for (int ci : x.p->bucket_convs[bk]) {
@@ -1423,10 +1389,10 @@ int unpack_bucket(const Ctx& x, int bk, float* grads) {
     if (cv.kind == L_CONV) { e.kind = UP_CONV; e.Co = cv.Co; e.Ci = cv.Ci; }
     else if (cv.kind == L_CONVT) { e.kind = UP_CONVT; e.Co = cv.Co; e.Ci = cv.Ci; }
     else { e.kind = UP_STEM; e.Co = cv.Co; e.Ci = 1; e.R = 7; e.S = 7; }
-    if (t.n == kMaxPack) { CK(launch_unpack(t, x.wst)); t.n = 0; }
+    if (t.n == kMaxPack) { CK(launch_unpack(t, x.st)); t.n = 0; }
   }
   if (!defer || bk == (int)x.p->buckets.size() - 1) {  // the last bucket (the stem's) ends the backward
-    CK(launch_unpack(t, x.wst));
+    CK(launch_unpack(t, x.st));
     t.n = 0;
   }
   return 0;
@@ -1610,7 +1576,6 @@ static int run_forward(unet_plan* p, const float* image, const float* const* prm
     a.w = x.W<bf16_t>(cv.pk_fwd);
     a.y = x.A(p->y0); a.ldy = p->y0.ld;
     a.stats = training ? x.W<double>(p->bns[p->stem_bn].stats) : nullptr;
-    if (a.stats) a.bn = bn_launch(x, p->stem_bn, (int64_t)N * p->y0.H * p->y0.W);
     a.N = N; a.H = p->cfg.H; a.W = p->cfg.W; a.C = 1;
     a.P = p->y0.H; a.Q = p->y0.W; a.Cout = cv.Co;
     a.R = 7; a.S = 7; a.stride = 2; a.pad = 3;
@@ -1726,28 +1691,6 @@ static int run_forward(unet_plan* p, const float* image, const float* const* prm
   return 0;
 }
 
-// a fresh event of the per-pass pool (reset at every backward)
-int pooled_event(unet_plan* p, hipEvent_t* out) {
-  if (p->syncused == (int)p->syncpool.size()) {
-    hipEvent_t e;
-    CK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    p->syncpool.push_back(e);
-  }
-  *out = p->syncpool[p->syncused++];
-  return 0;
-}
-
-// `to` waits for everything issued so far on `from` (fresh pool event per
-// edge, so the order is also right under stream capture)
-int stream_edge(unet_plan* p, hipStream_t from, hipStream_t to) {
-  if (from == to) return 0;
-  hipEvent_t e;
-  RUN(pooled_event(p, &e));
-  CK(hipEventRecord(e, from));
-  CK(hipStreamWaitEvent(to, e, 0));
-  return 0;
-}
-
 static int run_backward(unet_plan* p, const float* image, const float* dlogits, const float* const* prm, char* ws,
                         float* grads, hipStream_t st) {
   Ctx x{p, ws, prm, nullptr, st, 1};
@@ -1758,11 +1701,6 @@ static int run_backward(unet_plan* p, const float* image, const float* dlogits, 
   p->wgb_names.clear();
   p->wgb_flops = 0;
   if (p->want_events) RUN(ensure_events(p));
-  x.wst = st;
-  x.rst = st;
-  p->syncused = 0;
-  // fork: the weight stream starts after the zeroing of the accumulators
-  auto fork = [&]() { return stream_edge(p, st, x.wst); };
   if (!p->bwd_zeroed || p->bwd_zeroed_ws != ws) CK(hipMemsetAsync(ws + p->zero_bwd_off, 0, p->zero_bwd_bytes, st));
   p->bwd_zeroed = false;
   p->bwd_zeroed_ws = nullptr;
@@ -1827,8 +1765,6 @@ static int run_backward(unet_plan* p, const float* image, const float* dlogits, 
     if (att) {  // ChannelAttention backward: dOut2 -> dZ of the decoder's last BN (its reduction fused)
       ChAttArgs c = ch_args(x, l, grads);
       c.bb = dec_bn2(l);
-      c.bb.ticket = nullptr;  // the apply recomputes its coefficients from the sums
-      c.bb.coef = nullptr;
       {
         ProfScope ps(p, st, "ch_att_bwd", 0);
         for (int pass = 3; pass < 6; ++pass) CK(launch_ch_att(c, pass, st));
@@ -1836,12 +1772,10 @@ static int run_backward(unet_plan* p, const float* image, const float* dlogits, 
       RUN(bn_backward(x, d.bn2, c.bb, true));
     }
     if (!att) RUN(bn_backward(x, d.bn2, dec_bn2(l), fz));
-    RUN(fork());
     RUN(conv_wgrad(x, d.conv2, d.dy2, d.h));
     const BnBwdArgs f1 = dec_bn1(l);
     RUN(conv_dgrad(x, d.conv2, d.dy2, d.dh, nullptr, fz ? &f1 : nullptr));
     RUN(bn_backward(x, d.bn1, f1, fz));
-    RUN(fork());
     RUN(conv_wgrad(x, d.conv1, d.dy1, d.cat));
     RUN(conv_dgrad(x, d.conv1, d.dy1, d.dcat, nullptr, nullptr, -1, nullptr, d.split ? &d.dcat_up : nullptr));
     // (decoder conv bias gradients: exactly 0, written by bucket 0's unpack)
@@ -1853,15 +1787,12 @@ static int run_backward(unet_plan* p, const float* image, const float* dlogits, 
       // relu(BN_g + BN_x) backward: its reduction runs inside the gate's apply
       // pass (which produces dA and already reads the relu output)
       a.bb = bwd_args(x, t.bng, t.dS, t.s, t.g1, t.dg1, t.bnx, &t.xa, &t.dxa, nullptr, grads);
-      a.bb.ticket = nullptr;  // the apply recomputes its coefficients from the sums
-      a.bb.coef = nullptr;
       {
         ProfScope ps(p, st, "att_gate_bwd", 0);
         CK(launch_att_gate(a, 2, st));
         CK(launch_att_gate(a, 3, st));
       }
       RUN(bn_backward(x, t.bng, a.bb, true));
-      RUN(fork());
       RUN(conv_wgrad(x, t.wg, t.dg1, d.up_out));
       RUN(conv_wgrad(x, t.wx, t.dxa, t.x));
       RUN(conv_dgrad(x, t.wg, t.dg1, t.du, &d.dcat_up));
@@ -1870,7 +1801,6 @@ static int run_backward(unet_plan* p, const float* image, const float* dlogits, 
     }
     const Conv& up = p->convs[d.up];
     const Act du = att ? p->atts[l].du : d.dcat_up;
-    RUN(fork());
     RUN(conv_wgrad(x, d.up, du, d.up_in));
     const BnBwdArgs fu = l > 0 ? dec_bn2(l - 1) : blk_bn2(nb - 1);
     // with attention the up-conv input of levels 3..1 is the channel-gated
@@ -1882,31 +1812,27 @@ static int run_backward(unet_plan* p, const float* image, const float* dlogits, 
     RUN(conv_dgrad(x, d.up, du, d.d_up_in, nullptr, fuse_up ? &fu : nullptr, -1, nullptr, nullptr,
                    x.W<double>(up.bias_acc), &bias_fused));
     if (!bias_fused) {
-      ProfScope ps(p, x.wst, "bias_sum", 0);
-      CK(launch_channel_sum(x.A(du), du.ld, (int64_t)N * du.H * du.W, up.Co, x.W<double>(up.bias_acc), x.wst));
+      ProfScope ps(p, x.st, "bias_sum", 0);
+      CK(launch_channel_sum(x.A(du), du.ld, (int64_t)N * du.H * du.W, up.Co, x.W<double>(up.bias_acc), x.st));
     }
   }
-  // bucket 0 also holds the head's and the decoder biases' gradients (main stream)
-  RUN(stream_edge(p, st, x.wst));
+  // bucket 0 also holds the head's and the decoder biases' gradients
   RUN(unpack_bucket(x, 0, grads));
-  if (p->nevents) CK(hipEventRecord(p->events[0], x.wst));
+  if (p->nevents) CK(hipEventRecord(p->events[0], x.st));
   // encoder blocks, deepest first
   for (int i = nb - 1; i >= 0; --i) {
     Block& b = p->blocks[i];
     if (b.bottleneck()) {
       RUN(bn_backward(x, b.bn3, blk_bn2(i), fz));  // dY3 (+ dY of the downsample BN)
-      RUN(fork());
       RUN(conv_wgrad(x, b.conv3, b.dy3, b.h2));
       if (b.ds >= 0) RUN(conv_wgrad(x, b.ds, b.dyds, b.in));
       const BnBwdArgs f2 = bwd_args(x, b.bn2, b.dh2, b.h2, b.y2, b.dy2, -1, nullptr, nullptr, nullptr, grads);
       RUN(conv_dgrad(x, b.conv3, b.dy3, b.dh2, nullptr, fz ? &f2 : nullptr));
       RUN(bn_backward(x, b.bn2, f2, fz));
-      RUN(fork());
       RUN(conv_wgrad(x, b.conv2, b.dy2, b.h));
       const BnBwdArgs f1 = blk_bn1(i);
       RUN(conv_dgrad(x, b.conv2, b.dy2, b.dh, nullptr, fz ? &f1 : nullptr));
       RUN(bn_backward(x, b.bn1, f1, fz));
-      RUN(fork());
       RUN(conv_wgrad(x, b.conv1, b.dy1, b.in));
       BnBwdArgs fp = {};
       const BnBwdArgs* fprev = nullptr;
@@ -1922,21 +1848,18 @@ static int run_backward(unet_plan* p, const float* image, const float* dlogits, 
       }
       if (i == 13 || i == 7) {
         const int bk = i == 13 ? 1 : 2;
-        RUN(stream_edge(p, st, x.wst));
         RUN(unpack_bucket(x, bk, grads));
-        if (p->nevents) CK(hipEventRecord(p->events[bk], x.wst));
+        if (p->nevents) CK(hipEventRecord(p->events[bk], x.st));
       }
       continue;
     }
     RUN(bn_backward(x, b.bn2, blk_bn2(i), fz));
-    RUN(fork());
     RUN(conv_wgrad(x, b.conv2, b.dy2, b.h));
     const bool dsfold = p->ds_wgrad_fold && ds_fold_ok(x, b);
     if (b.ds >= 0 && !dsfold) RUN(conv_wgrad(x, b.ds, b.dyds, b.in));
     const BnBwdArgs f1 = blk_bn1(i);
     RUN(conv_dgrad(x, b.conv2, b.dy2, b.dh, nullptr, fz ? &f1 : nullptr));
     RUN(bn_backward(x, b.bn1, f1, fz));
-    RUN(fork());
     RUN(conv_wgrad(x, b.conv1, b.dy1, b.in, dsfold ? b.ds : -1, &b.dyds));
     // the last writer of d_in produces dA of the previous block's bn2
     BnBwdArgs fp = {};
@@ -1949,21 +1872,18 @@ static int run_backward(unet_plan* p, const float* image, const float* dlogits, 
       // identity path: dZ of bn2 (held in d_out when fused)
       RUN(conv_dgrad(x, b.conv1, b.dy1, b.d_in, fz ? &b.d_out : &b.dres, fprev));
     }
-    // bucket boundaries (weight stream; BN parameter grads come from the main
-    // stream's reductions): enc4 done at i == 13, enc3 at i == 7
+    // bucket boundaries: enc4 done at i == 13, enc3 at i == 7
     if (i == 13 || i == 7) {
       const int bk = i == 13 ? 1 : 2;
-      RUN(stream_edge(p, st, x.wst));
       RUN(unpack_bucket(x, bk, grads));
-      if (p->nevents) CK(hipEventRecord(p->events[bk], x.wst));
+      if (p->nevents) CK(hipEventRecord(p->events[bk], x.st));
     }
   }
   // bucket 3 (enc2 + enc1) is final: its all-reduce overlaps the stem's backward
   {
     const int bk = (int)p->buckets.size() - 2;
-    RUN(stream_edge(p, st, x.wst));
     RUN(unpack_bucket(x, bk, grads));
-    if (p->nevents) CK(hipEventRecord(p->events[bk], x.wst));
+    if (p->nevents) CK(hipEventRecord(p->events[bk], x.st));
   }
   // maxpool + stem
   if (p->stem_rc && fz) {
@@ -1993,7 +1913,6 @@ static int run_backward(unet_plan* p, const float* image, const float* dlogits, 
       ProfScope ps(p, st, "wgrad_reduce input_conv.weight", 0);
       CK(launch_stem_rc_bwd(s, 1, st));
     }
-    RUN(fork());
   } else {
     MaxPoolArgs m = {};
     m.dy = x.A(p->d_p0); m.lddy = p->d_p0.ld; m.idx = x.W<uint8_t>(p->pidx);
@@ -2013,7 +1932,6 @@ static int run_backward(unet_plan* p, const float* image, const float* dlogits, 
     // fused: the stem wgrad forms dY from dZ and y itself (no apply pass, dY never stored)
     const bool stem_fuse = fz && p->stem_bn_fuse && cv.Co % 64 == 0;
     if (!stem_fuse) RUN(bn_backward(x, p->stem_bn, sb, fz));
-    RUN(fork());
     ConvWgradArgs a = {};
     a.dy = x.A(p->d_y0); a.lddy = p->d_y0.ld;
     if (stem_fuse) { a.bn = sb; a.bn_fuse = 1; }
@@ -2027,10 +1945,8 @@ static int run_backward(unet_plan* p, const float* image, const float* dlogits, 
   {
     const int bk = (int)p->buckets.size() - 1;
     RUN(unpack_bucket(x, bk, grads));
-    if (p->nevents) CK(hipEventRecord(p->events[bk], x.wst));
+    if (p->nevents) CK(hipEventRecord(p->events[bk], x.st));
   }
-  // join: the caller's stream (optimizer, next forward) sees every gradient
-  RUN(stream_edge(p, x.wst, st));
   return 0;
 }
 
@@ -2069,7 +1985,6 @@ void unet_plan_destroy(unet_plan* p) {
   if (!p) return;
   if (p->tim_buf) (void)hipFree(p->tim_buf);
   for (int i = 0; i < p->nevents; ++i) (void)hipEventDestroy(p->events[i]);
-  for (hipEvent_t e : p->syncpool) (void)hipEventDestroy(e);
   delete p;
 }
 

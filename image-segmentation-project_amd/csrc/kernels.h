@@ -31,16 +31,16 @@ enum { ALOAD_NHWC = 0, ALOAD_STEM = 1 };
 // (x = dY gathered 4 output pixels per input pixel, C = 4*Co, R = S = 1)
 enum { XLOAD_NHWC = 0, XLOAD_STEM = 1, XLOAD_SHUF = 2 };
 
-// BatchNorm parameters of one layer.  Training: the producer of the batch sums
-// (conv epilogue) finalises them in its LAST block (ticket counter) into
-// ss = {scale[C], shift[C]}, save_mean/save_invstd and the running stats;
-// consumers then only read ss.  Eval: scale/shift from the running stats.
+// BatchNorm parameters of one layer.  Training: the producer (conv epilogue)
+// only adds its per-channel sums into the replicas of `stats`; every consumer
+// sums the replicas and recomputes scale/shift for the channels it touches
+// (bn_scale_shift, common.h), and block 0 of the first consumer also
+// finalises the layer (bn_finalize): save_mean/save_invstd for the backward
+// and the running stats.  Eval: scale/shift from the running stats.
 struct BnLaunch {
   const double* stats; const float* gamma; const float* beta;
   float* run_mean; float* run_var; float* save_mean; float* save_invstd;
   double count; int C; float eps, momentum; int training;
-  float* ss;          // [2][C] scale | shift (written by the finaliser)
-  unsigned* ticket;   // zeroed per step; last arriving block finalises
   long long* nbt;     // num_batches_tracked (int64), += 1 with channel 0's running stats; null: untouched
 };
 
@@ -57,10 +57,8 @@ struct BnBwdArgs {
   bf16_t* dy; int lddy;              // apply: dY out
   bf16_t* dy2; int lddy2;            // apply: dY2 out (bn2)
   bf16_t* dres; int lddres;          // apply: dZ out (identity residual) or null
-  float* dgamma; float* dbeta;       // param grads (written by the reduce's last block)
+  float* dgamma; float* dbeta;       // param grads (written by the apply's blocks bx == 0 from the sums)
   float* dgamma2; float* dbeta2;
-  unsigned* ticket;                  // zeroed per step; reduce's last block finalises
-  float* coef;                       // [5][C]: k1, mean dZ, mean dZ*xhat, k1b, mean dZ*xhat2
   int64_t npix; int C; int relu;
 };
 // fp8 per-tensor scale state (fp8.hip): amax of the previous step (the scale
@@ -74,12 +72,11 @@ struct ConvFwdArgs {
   bf16_t* y; int ldy;            // output NHWC bf16
   const float* bias;             // [Cout] or null
   const bf16_t* add; int ldadd;  // optional addend (same pixel grid as y)
-  double* stats;                 // optional BN sums [kStatRep][2][Cout] (fp64 atomics)
-  BnLaunch bn;                   // finalised by the last block when bn.ticket != null
+  double* stats;                 // optional BN sums [kStatRep][2][Cout] (fp64 atomics); consumers finalise
   // fused BN(+ReLU) backward reduction (conv dgrad producing dA of a BN):
   // when bb.sums != null the epilogue writes dZ = dA * (act > 0) instead of dA
   // and adds sum dZ, sum dZ*xhat (and dZ*xhat2) into bb.sums / bb.sums2; the
-  // last block runs bn_bwd_finalize (common.h).
+  // apply pass (bn_bwd_apply_kernel) turns the sums into coefficients.
   BnBwdArgs bb;
   // optional second reduction range of parity class 0 (MODE_TRANS only): the
   // 1x1 / stride-2 downsample dgrad folded into its block's conv1 dgrad.
@@ -110,9 +107,9 @@ struct ConvFwdArgs {
   int R, S, stride, pad;
   // forward 3x3 / stride-2 conv1 of a downsample block with its 1x1 / stride-2
   // downsample folded in (MODE_FWD, launch_conv_fwd): wds = the downsample's
-  // packed weights [Cout][C]; its output yds (+ BN sums stats_ds / bnds as
-  // `stats` / `bn`) comes from the same staged input (the centre tap's K range)
-  const bf16_t* wds; bf16_t* yds; int ldyds; double* stats_ds; BnLaunch bnds;
+  // packed weights [Cout][C]; its output yds (+ BN sums stats_ds as `stats`)
+  // comes from the same staged input (the centre tap's K range)
+  const bf16_t* wds; bf16_t* yds; int ldyds; double* stats_ds;
   // MODE_FWD implicit GEMM only: a column stride other than `stride` (0 = the
   // same).  The ConvTranspose data gradient runs as R = 2, S = 1, stride (2, 1)
   // over a view of dY that merges each pair of adjacent pixels into one of 2C
@@ -199,8 +196,8 @@ hipError_t launch_conv3x3_fl(const ConvFwdArgs& a, int mode, hipStream_t st);
 // the implicit-GEMM path).
 hipError_t launch_convt2x2(const ConvFwdArgs& a, int mode, hipStream_t st);
 // forward with xform (the previous BN + ReLU applied to the pixel operand,
-// the activation stored to xh, block 0 finalising that BN; training, no
-// ticket): shape / stride test; the launch itself fails (no fallback) when an
+// the activation stored to xh, block 0 finalising that BN; training):
+// shape / stride test; the launch itself fails (no fallback) when an
 // xform launch is not taken
 bool convt2x2_xform_ok(const ConvFwdArgs& a);
 // 1 x 1 / stride-1 conv as a weight-stationary per-pixel GEMM (convt.hip): mode
@@ -330,7 +327,7 @@ hipError_t launch_maxpool_bwd(const MaxPoolArgs& a, hipStream_t st);
 
 // The stem by recompute (stem_rc.hip): conv 7x7/s2 (1 -> Cout) + BN + ReLU +
 // MaxPool(3,2,1) without storing the raw conv output.  Forward: a statistics
-// pass (mode 0: BN sums, last block finalises bn; y stored only when y != null,
+// pass (mode 0: BN sums; y stored only when y != null,
 // tests) and an apply pass (mode 1: act, pooled, idx).  Backward: dZ of the
 // stem BN from dpool / idx / add (the maxpool backward, stored to dz only when
 // dz != null) and, in the same pass, partial sums of dZ^T im2col, xhat^T
@@ -340,7 +337,7 @@ struct StemRcArgs {
   const float* img; int H, W;        // fp32 [N][H][W]
   const bf16_t* w;                   // packed [Cout][64] bf16
   int N, P, Q, Cout, Pp, Qp;         // conv output P x Q, pooled Pp x Qp
-  double* stats; BnLaunch bn;        // BN of the stem (bn.ss: scale | shift)
+  double* stats; BnLaunch bn;        // BN of the stem
   bf16_t* y; int ldy;
   bf16_t* act; int ldact;
   bf16_t* pool; int ldpool; uint8_t* idx;   // idx [pixel][Cout]

@@ -5,9 +5,10 @@
 // output value, so recomputing it wherever y is needed costs a few MFMAs per
 // pixel against ~0.3 GB of HBM traffic saved per step.
 //
-//   stats pass   conv -> BN batch sums (fp64 replica atomics, last block
-//                finalises scale/shift/save/running stats as stem_fwd did)
-//   apply pass   conv -> fp32 y -> relu(y * scale + shift) = act (the
+//   stats pass   conv -> BN batch sums (fp64 replica atomics)
+//   apply pass   every block recomputes scale/shift from the sums (block 0 of a
+//                channel group also writes the saved / running statistics);
+//                conv -> fp32 y -> relu(y * scale + shift) = act (the
 //                decoder1 skip, stored once) -> MaxPool(3,2,1) of act in LDS
 //                -> pooled + argmax index.  A block walks pooled rows, keeping
 //                the last three act rows in an LDS ring; its first pooled row
@@ -193,21 +194,17 @@ __global__ void __launch_bounds__(kRcNT) stem_rc_fwd_kernel(StemRcArgs a, int pe
   load_wfrag(a.w, cg, wf);
   if (MODE == 1 && tid < 64) {
     const int c = cg + tid;
-    if (a.bn.training && a.bn.ss) {
-      coef[tid] = a.bn.ss[c];
-      coef[64 + tid] = a.bn.ss[a.Cout + c];
-    } else {  // from the batch sums (or running statistics): every block alike
-      float m, inv, var;
-      bn_scale_shift(a.bn, c, coef[tid], coef[64 + tid], m, inv, var);
-      if (blockIdx.x == 0 && a.bn.training) {  // block 0 of the group: saved / running statistics
-        a.bn.save_mean[c] = m;
-        a.bn.save_invstd[c] = inv;
-        const double cnt = a.bn.count;
-        const float unb = (float)((double)var * (cnt / (cnt > 1.0 ? cnt - 1.0 : 1.0)));
-        a.bn.run_mean[c] = (1.f - a.bn.momentum) * a.bn.run_mean[c] + a.bn.momentum * m;
-        a.bn.run_var[c] = (1.f - a.bn.momentum) * a.bn.run_var[c] + a.bn.momentum * unb;
-        if (c == 0 && a.bn.nbt) *a.bn.nbt += 1;
-      }
+    // from the batch sums (or running statistics): every block alike
+    float m, inv, var;
+    bn_scale_shift(a.bn, c, coef[tid], coef[64 + tid], m, inv, var);
+    if (blockIdx.x == 0 && a.bn.training) {  // block 0 of the group: saved / running statistics
+      a.bn.save_mean[c] = m;
+      a.bn.save_invstd[c] = inv;
+      const double cnt = a.bn.count;
+      const float unb = (float)((double)var * (cnt / (cnt > 1.0 ? cnt - 1.0 : 1.0)));
+      a.bn.run_mean[c] = (1.f - a.bn.momentum) * a.bn.run_mean[c] + a.bn.momentum * m;
+      a.bn.run_var[c] = (1.f - a.bn.momentum) * a.bn.run_var[c] + a.bn.momentum * unb;
+      if (c == 0 && a.bn.nbt) *a.bn.nbt += 1;
     }
   }
   float q0[4][4], q1[4][4];
@@ -388,10 +385,6 @@ __global__ void __launch_bounds__(kRcNT) stem_rc_fwd_kernel(StemRcArgs a, int pe
       atomicAdd(rep + tid, (double)s0);
       atomicAdd(rep + a.Cout + tid, (double)s1);
     }
-    if (a.bn.ticket) {
-      int* flag = reinterpret_cast<int*>(smem + (kRcNT / 64) * 64 * 2 * sizeof(float));
-      if (last_block_arrive(a.bn.ticket, gridDim.x * gridDim.y, flag, tid < 64)) bn_finalize(a.bn);
-    }
   }
   TSTAMP(a.tim, 21);
   TSTAMP_RT(a.tim, 31);
@@ -503,13 +496,9 @@ __global__ void __launch_bounds__(kRbNT, 2) stem_rc_bwd_kernel(StemRcArgs a, int
     lds_sync();
   }
   if (tid < 64) {
-    if (a.bn.ss) {
-      cf[tid] = a.bn.ss[cg + tid];
-      cf[64 + tid] = a.bn.ss[a.Cout + cg + tid];
-    } else {  // the forward's scale / shift, recomputed from the same batch sums
-      float m, inv, var;
-      bn_scale_shift(a.bn, cg + tid, cf[tid], cf[64 + tid], m, inv, var);
-    }
+    // the forward's scale / shift, recomputed from the same batch sums
+    float m, inv, var;
+    bn_scale_shift(a.bn, cg + tid, cf[tid], cf[64 + tid], m, inv, var);
     cf[128 + tid] = a.mean[cg + tid];
     cf[192 + tid] = a.invstd[cg + tid];
     // mu[k]: the image mean for the 49 real taps, 0 for the padding.  The
