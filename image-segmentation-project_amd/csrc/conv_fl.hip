@@ -37,7 +37,6 @@
 // starts on H0 / W0 and ends on W1 / H1, which the epilogue then uses as its
 // 64 KB transpose buffer while the next tile's first stage lands in H0 / W0.
 #include <cstdio>
-#include <cstdlib>
 
 #include "common.h"
 #include "kernels.h"
@@ -537,8 +536,7 @@ bool conv3x3_fl_geom(int C, int Cout, int P, int Q) {
 }
 
 bool conv3x3_fl_shape(int N, int C, int Cout, int P, int Q) {
-  static const bool off = std::getenv("UNET_NO_FL") != nullptr;  // A/B: the halo-streamed kernel
-  if (off || !conv3x3_fl_geom(C, Cout, P, Q)) return false;
+  if (!conv3x3_fl_geom(C, Cout, P, Q)) return false;
   return (long long)N * (P / kTH) * (Q / 16) * (Cout / kCOT) >= cu_count();
 }
 
@@ -1021,12 +1019,7 @@ __global__ void __launch_bounds__(kNW * 64) conv3x3_ws2_kernel(ConvFwdArgs a, in
 // with bias and / or BN sums, data gradient with or without addend and fused
 // BN backward); everything else stays on conv3x3_ws_kernel
 bool conv3x3_ws2_ok(const ConvFwdArgs& a, bool flip) {
-  // A/B: the previous kernel (read per launch: tests set it); "f" / "b" / "x":
-  // only the forward / the data gradient / the xform forward
-  const char* ev = std::getenv("UNET_NO_WS2");
-  const bool off = ev && (ev[0] == '1' || (ev[0] == 'f' && !flip) || (ev[0] == 'b' && flip) ||
-                          (ev[0] == 'x' && !flip && a.xform));
-  if (off || a.C != 64 || a.Cout % kCOT || a.P % kTH || a.Q % 16 || a.H != a.P || a.W != a.Q) return false;
+  if (a.C != 64 || a.Cout % kCOT || a.P % kTH || a.Q % 16 || a.H != a.P || a.W != a.Q) return false;
   if (a.R != 3 || a.S != 3 || a.stride != 1 || a.pad != 1 || a.x2 || a.ysplit || a.fold_on) return false;
   if (a.xform && (flip || !a.xh || a.ldxh % 8)) return false;
   if (a.ldx % 8 || a.ldy % 8 || (a.add && a.ldadd % 4)) return false;

@@ -989,14 +989,12 @@ static hipError_t launch_s2d_ext(const ConvFwdArgs& a, hipStream_t st) {
   return a.x2 ? launch_s2d<FN, RW, NW, true>(a, st) : launch_s2d<FN, RW, NW, false>(a, st);
 }
 
-static int g_s2_disabled = std::getenv("UNET_NO_S2HALO") != nullptr;  // A/B switch for measurements
-
 // 3x3 / stride-2 / pad-1 data gradient (+ the folded 1x1 / s2 downsample
 // dgrad) when the shape is covered; hipErrorNotSupported otherwise (the caller
 // falls back to the implicit-GEMM MODE_TRANS kernel).  a: x = dY [N,H,W,C],
 // y = dX [N,P=2H,Q=2W,Cout], w = dgrad pack [Cout][9][C].
 hipError_t launch_conv3x3s2_dgrad(const ConvFwdArgs& a, hipStream_t st) {
-  if (g_s2_disabled || a.ysplit || a.fold_on || a.stats || a.bias) return hipErrorNotSupported;
+  if (a.ysplit || a.fold_on || a.stats || a.bias) return hipErrorNotSupported;
   if (a.R != 3 || a.S != 3 || a.stride != 2 || a.pad != 1) return hipErrorNotSupported;
   if (a.P != 2 * a.H || a.Q != 2 * a.W || a.W % 16 || a.C % 32 || a.Cout % 64) return hipErrorNotSupported;
   if (a.ldx % 8 || a.ldy % 4 || (a.x2 && (a.C2 != a.C || a.ldx2 % 8))) return hipErrorNotSupported;

@@ -1,15 +1,15 @@
 // Implicit-GEMM convolution kernels for gfx950 (CDNA4), bf16 NHWC, fp32 accumulate.
 //
-// One template covers every conv-shaped op on the U-Net hot path
-// (SURVEY.md §8(a) rows a2-a6):
+// conv_glds_kernel (operands staged by LDS-DMA) covers the conv-shaped ops that
+// no dedicated kernel takes:
 //   MODE_FWD   y[n,oh,ow,:] = sum_{r,s} x[n, oh*st-pad+r, ow*st-pad+s, :] . W[:,r,s,:]
 //              (3x3 s1/s2 encoder+decoder convs, 1x1 s2 downsample, and the
 //              k2s2 convT *dgrad*, which is an ordinary k2s2 conv of dY)
 //   MODE_TRANS the transposed (gather) form, output split into stride^2 parity
 //              classes so that every tap inside a class is dense (no zero MACs):
 //              3x3 s1/s2 conv *dgrad* and the ConvTranspose2d(k2,s2) *forward*.
-//   ALOAD_STEM the 7x7/s2 stem: im2col of the fp32 single-channel image built in
-//              the loader (K = 49 taps padded to 64).
+// The 7x7/s2 stem has kernels of its own (stem_fwd_kernel, stem_wgrad_kernel:
+// im2col of the fp32 single-channel image built in LDS, K = 49 taps padded to 64).
 // GEMM view: D[co][pixel] = sum_k Wp[co][k] * X[pixel][k]; the MFMA A operand
 // is the packed weight tile (rows = output channels), B the activation tile
 // (cols = pixels), so each lane's accumulator holds 4 consecutive channels of
@@ -59,196 +59,6 @@ struct TapIter {
   // MODE_FWD: all R*S taps.  MODE_TRANS: taps r = r0 + st*j valid for class py.
   int r0, s0, nr, ns, st;
 };
-
-template <int MODE, int BN, int WM, int WN, int FM, int FN>
-__device__ __forceinline__ void conv_epilogue(const ConvFwdArgs& a, f32x4 (&acc)[FN][FM], char* smem, int m0,
-                                              int n0, int Mtot, int py, int px_);
-
-template <int MODE, int ALOAD, int BM, int BN, int BK, int WM, int WN>
-__global__ void __launch_bounds__(256)
-conv_fwd_kernel(ConvFwdArgs a) {
-  constexpr int WTM = BM / WM;  // pixels per wave
-  constexpr int WTN = BN / WN;  // channels per wave
-  constexpr int FM = WTM / 16;
-  constexpr int FN = WTN / 16;
-  static_assert(WM * WN == 4, "4 waves");
-  static_assert(FM >= 1 && FN >= 1, "fragment tiling");
-  constexpr int CPR = BK / 8;                       // 16-B chunks per LDS row
-  constexpr int ROWB = BK * 2;                      // bytes per LDS row
-  constexpr int A_ROWS_PER_PASS = 256 / CPR;
-  constexpr int A_PASSES = (BM + A_ROWS_PER_PASS - 1) / A_ROWS_PER_PASS;
-  constexpr int B_PASSES = (BN + A_ROWS_PER_PASS - 1) / A_ROWS_PER_PASS;
-  constexpr int A_BYTES = BM * ROWB;
-  constexpr int B_BYTES = BN * ROWB;
-  constexpr int STAGE = A_BYTES + B_BYTES;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int wm = wave % WM;
-  const int wn = wave / WM;
-
-  // ---- tile coordinates ----
-  const int nwg = gridDim.x;
-  const int bid = xcd_remap(blockIdx.x, nwg);
-  const int nblk = bid % a.nblocks;
-  const int mblk = bid / a.nblocks;
-  const int cls = blockIdx.z;
-  const int st = a.stride;
-  const int py = (MODE == MODE_TRANS) ? cls / st : 0;
-  const int px_ = (MODE == MODE_TRANS) ? cls % st : 0;
-  const int Pc = a.Pc, Qc = a.Qc;
-  const int Mtot = a.N * Pc * Qc;
-  const int m0 = mblk * BM;
-  const int n0 = nblk * BN;
-
-  TapIter ti;
-  if constexpr (MODE == MODE_TRANS) {
-    ti.st = st;
-    ti.r0 = (py + a.pad) % st;
-    ti.s0 = (px_ + a.pad) % st;
-    ti.nr = (a.R - ti.r0 + st - 1) / st;
-    ti.ns = (a.S - ti.s0 + st - 1) / st;
-  } else if constexpr (ALOAD == ALOAD_STEM) {
-    ti.st = 1; ti.r0 = 0; ti.s0 = 0; ti.nr = 1; ti.ns = 1;  // one K step of 64 taps
-  } else {
-    ti.st = 1; ti.r0 = 0; ti.s0 = 0; ti.nr = a.R; ti.ns = a.S;
-  }
-  const int cchunks = (ALOAD == ALOAD_STEM) ? 1 : a.C / BK;
-  const int KT = ti.nr * ti.ns * cchunks;
-  const int Ktot = (ALOAD == ALOAD_STEM) ? 64 : a.R * a.S * a.C;  // packed weight row length
-
-  // ---- per-thread A-row bookkeeping (fixed rows across K steps) ----
-  const int ach = tid % CPR;
-  int an[A_PASSES], aa[A_PASSES], ab[A_PASSES];
-#pragma unroll
-  for (int i = 0; i < A_PASSES; ++i) {
-    const int row = tid / CPR + i * A_ROWS_PER_PASS;
-    const int m = m0 + row;
-    if (row < BM && m < Mtot) {
-      const int n = m / (Pc * Qc);
-      const int rem = m - n * (Pc * Qc);
-      an[i] = n;
-      aa[i] = rem / Qc;
-      ab[i] = rem - aa[i] * Qc;
-    } else {
-      an[i] = -1; aa[i] = 0; ab[i] = 0;
-    }
-  }
-
-  uint4 ra[A_PASSES];
-  uint4 rb[B_PASSES];
-
-  auto load_tiles = [&](int kt) {
-    const int cc = kt % cchunks;
-    const int tap = kt / cchunks;
-    const int jr = tap / ti.ns, js = tap - jr * ti.ns;
-    const int r = ti.r0 + ti.st * jr;
-    const int s = ti.s0 + ti.st * js;
-    const int c0 = cc * BK;
-    // activations
-#pragma unroll
-    for (int i = 0; i < A_PASSES; ++i) {
-      uint4 v = make_uint4(0, 0, 0, 0);
-      const int row = tid / CPR + i * A_ROWS_PER_PASS;
-      if (row < BM && an[i] >= 0) {
-        if constexpr (ALOAD == ALOAD_STEM) {
-          // im2col of the fp32 image: k = ach*8 + e -> (kr, ks) = (ach, e), ks < 7
-          const float* img = reinterpret_cast<const float*>(a.x);
-          float f[8];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const int kr = ach, ks = e;
-            const int ih = aa[i] * st - a.pad + kr;
-            const int iw = ab[i] * st - a.pad + ks;
-            f[e] = (kr < 7 && ks < 7 && ih >= 0 && ih < a.H && iw >= 0 && iw < a.W)
-                       ? img[((size_t)an[i] * a.H + ih) * a.W + iw] : 0.f;
-          }
-          v = pack8(f);
-        } else {
-          int ih, iw;
-          if constexpr (MODE == MODE_FWD) {
-            ih = aa[i] * st - a.pad + r;
-            iw = ab[i] * st - a.pad + s;
-          } else {
-            ih = aa[i] + (py + a.pad - r) / st;
-            iw = ab[i] + (px_ + a.pad - s) / st;
-          }
-          if (ih >= 0 && ih < a.H && iw >= 0 && iw < a.W) {
-            const bf16_t* p = a.x + ((size_t)(an[i] * a.H + ih) * a.W + iw) * a.ldx + c0 + ach * 8;
-            v = *reinterpret_cast<const uint4*>(p);
-          }
-        }
-      }
-      ra[i] = v;
-    }
-    // packed weights [Cout][Ktot], k = (r*S + s)*C + c
-    const int kbase = (ALOAD == ALOAD_STEM) ? 0 : (r * a.S + s) * a.C + c0;
-#pragma unroll
-    for (int i = 0; i < B_PASSES; ++i) {
-      const int row = tid / CPR + i * A_ROWS_PER_PASS;
-      uint4 v = make_uint4(0, 0, 0, 0);
-      if (row < BN && n0 + row < a.Cout) {
-        v = *reinterpret_cast<const uint4*>(a.w + (size_t)(n0 + row) * Ktot + kbase + ach * 8);
-      }
-      rb[i] = v;
-    }
-  };
-
-  auto store_tiles = [&](int buf) {
-    char* As = smem + buf * STAGE;
-    char* Bs = As + A_BYTES;
-#pragma unroll
-    for (int i = 0; i < A_PASSES; ++i) {
-      const int row = tid / CPR + i * A_ROWS_PER_PASS;
-      if (row < BM) *reinterpret_cast<uint4*>(As + frag_off<BK>(row, ach)) = ra[i];
-    }
-#pragma unroll
-    for (int i = 0; i < B_PASSES; ++i) {
-      const int row = tid / CPR + i * A_ROWS_PER_PASS;
-      if (row < BN) *reinterpret_cast<uint4*>(Bs + frag_off<BK>(row, ach)) = rb[i];
-    }
-  };
-
-  f32x4 acc[FN][FM];
-#pragma unroll
-  for (int i = 0; i < FN; ++i)
-#pragma unroll
-    for (int j = 0; j < FM; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  if (KT > 0) {  // KT == 0: a stride-2 parity class with no taps (1x1 s2 dgrad)
-    load_tiles(0);
-    store_tiles(0);
-  }
-  __syncthreads();
-
-  for (int kt = 0; kt < KT; ++kt) {
-    const int buf = kt & 1;
-    if (kt + 1 < KT) load_tiles(kt + 1);
-    const char* As = smem + buf * STAGE;
-    const char* Bs = As + A_BYTES;
-#pragma unroll
-    for (int kk = 0; kk < BK / 32; ++kk) {
-      const int ch = kk * 4 + (lane >> 4);
-      bf16x8 wf[FN], xf[FM];
-#pragma unroll
-      for (int i = 0; i < FN; ++i)
-        wf[i] = *reinterpret_cast<const bf16x8*>(Bs + frag_off<BK>(wn * WTN + i * 16 + (lane & 15), ch));
-#pragma unroll
-      for (int j = 0; j < FM; ++j)
-        xf[j] = *reinterpret_cast<const bf16x8*>(As + frag_off<BK>(wm * WTM + j * 16 + (lane & 15), ch));
-#pragma unroll
-      for (int i = 0; i < FN; ++i)
-#pragma unroll
-        for (int j = 0; j < FM; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[i], xf[j], acc[i][j], 0, 0, 0);
-    }
-    if (kt + 1 < KT) store_tiles(buf ^ 1);
-    __syncthreads();
-  }
-  conv_epilogue<MODE, BN, WM, WN, FM, FN>(a, acc, smem, m0, n0, Mtot, py, px_);
-}
 
 // ---- epilogue: bias, addend, bf16 NHWC store, BN partial sums (fp64 atomics) ----
 // Forward (a.stats): per-channel (sum y, sum y^2) of the stored values' fp32
@@ -901,8 +711,8 @@ conv_wgrad_kernel(ConvWgradArgs a) {
   const int tap = rest / a.c_blocks;
   const int co0 = cob * BMO;
   const int c0 = cblk * BNC;
-  const int r = (XLOAD == XLOAD_STEM) ? 0 : tap / a.S;
-  const int s = (XLOAD == XLOAD_STEM) ? 0 : tap - r * a.S;
+  const int r = tap / a.S;
+  const int s = tap - r * a.S;
   const int PQ = a.P * a.Q;
   const int Mtot = a.N * PQ;
   const int mbeg = blockIdx.z * a.px_per_split;
@@ -933,19 +743,7 @@ conv_wgrad_kernel(ConvWgradArgs a) {
         const int n = m / PQ;
         const int rem = m - n * PQ;
         const int p = rem / a.Q, q = rem - p * a.Q;
-        if constexpr (XLOAD == XLOAD_STEM) {
-          const float* img = reinterpret_cast<const float*>(a.x);
-          float f[8];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const int k = c0 + ch * 8 + e;
-            const int kr = k >> 3, ks = k & 7;  // stem K layout: k = kr*8 + ks, ks < 7
-            const int ih = p * a.stride - a.pad + kr, iw = q * a.stride - a.pad + ks;
-            f[e] = (kr < 7 && ks < 7 && ih >= 0 && ih < a.H && iw >= 0 && iw < a.W)
-                       ? img[((size_t)n * a.H + ih) * a.W + iw] : 0.f;
-          }
-          v = pack8(f);
-        } else if constexpr (XLOAD == XLOAD_SHUF) {
+        if constexpr (XLOAD == XLOAD_SHUF) {
           const int c = c0 + ch * 8, Co = a.C >> 2;
           if (c < a.C) {
             const int t = c / Co, co = c - t * Co;
@@ -1033,15 +831,14 @@ conv_wgrad_kernel(ConvWgradArgs a) {
 
   // D[co][c]: lane holds column c = .. + li, rows co = .. + 4g + e.  One split
   // with a slab: this block owns its dW tile (plain stores); else fp32 atomics
-  const int Krow = (XLOAD == XLOAD_STEM) ? 64 : a.R * a.S * a.C;
-  const int kcol0 = (XLOAD == XLOAD_STEM) ? 0 : tap * a.C;
+  const int Krow = a.R * a.S * a.C;
+  const int kcol0 = tap * a.C;
 #pragma unroll
   for (int i = 0; i < FM; ++i)
 #pragma unroll
     for (int j = 0; j < FN; ++j) {
       const int c = c0 + wn * WTN + j * 16 + li;
-      const int cmax = (XLOAD == XLOAD_STEM) ? 64 : a.C;
-      if (c < cmax) {
+      if (c < a.C) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int co = co0 + wm * WTM + i * 16 + 4 * g + e;
@@ -2278,22 +2075,6 @@ hipError_t launch_stem_wgrad(const ConvWgradArgs& a, hipStream_t st) {
 // host-side launch selection
 // ---------------------------------------------------------------------------
 
-template <int MODE, int ALOAD, int BM, int BN, int BK, int WM, int WN>
-static hipError_t launch_fwd_cfg(const ConvFwdArgs& a0, int classes, hipStream_t st) {
-  ConvFwdArgs a = a0;
-  a.nblocks = (a.Cout + BN - 1) / BN;
-  const int M = a.N * a.Pc * a.Qc;
-  a.mblocks = (M + BM - 1) / BM;
-  const size_t lds = 2 * (size_t)(BM + BN) * BK * 2;
-  size_t need = lds;
-  const size_t red = (size_t)WM * BN * 3 * sizeof(float);
-  if (red > need) need = red;
-  dim3 grid(a.mblocks * a.nblocks, 1, classes);
-  set_kernel_tag("conv_fwd_kernel<%d, %d, %d, %d, %d, %d, %d>", MODE, ALOAD, BM, BN, BK, WM, WN);
-  hipLaunchKernelGGL((conv_fwd_kernel<MODE, ALOAD, BM, BN, BK, WM, WN>), grid, dim3(256), need, st, a);
-  return hipGetLastError();
-}
-
 template <int MODE, int BM, int BN, int BK, int NS, int WM, int WN, bool DS = false>
 static hipError_t launch_glds_cfg(const ConvFwdArgs& a0, int classes, hipStream_t st) {
   ConvFwdArgs a = a0;
@@ -2486,9 +2267,9 @@ hipError_t launch_conv_fwd(const ConvFwdArgs& a0, int mode, hipStream_t st) {
                     a0.bb.sums || a0.add))
     return hipErrorInvalidValue;
   if (a0.fold_on && (mode != MODE_FWD || a0.stats || a0.bb.sums)) return hipErrorInvalidValue;
-  // dedicated stem kernel: 64 output channels (Base); the Wide stem (128) takes
-  // the generic implicit-GEMM path below
-  if (mode == MODE_STEM && a0.Cout % 64 == 0) return launch_stem_fwd(a0, st);
+  // the stem kernel works on 64-channel output groups (Base: 1, Wide: 2)
+  // and refuses any other width
+  if (mode == MODE_STEM) return launch_stem_fwd(a0, st);
   if (mode == MODE_SHUF) {  // convT k2s2 forward: a0 holds the transposed-conv geometry
     if (a0.R != 2 || a0.S != 2 || a0.stride != 2 || a0.pad != 0 || a0.Cout % 4 || a0.C % 32 ||
         a0.P != 2 * a0.H || a0.Q != 2 * a0.W || a0.stats || a0.add || a0.bb.sums)
@@ -2501,77 +2282,41 @@ hipError_t launch_conv_fwd(const ConvFwdArgs& a0, int mode, hipStream_t st) {
     return launch_glds<MODE_SHUF>(a, 1, st);
   }
   if (a0.wds && (mode != MODE_FWD || a0.C % 64)) return hipErrorInvalidValue;
-  if (mode != MODE_STEM && a0.C % 32 == 0) {
-    ConvFwdArgs a = a0;
-    if ((size_t)a.N * a.H * a.W * a.ldx * 2 >= 0x80000000ull) return hipErrorInvalidValue;
-    if (a.wds) {  // the folded downsample exists in the implicit-GEMM forward only
-      if ((size_t)a.N * a.P * a.Q * a.ldyds * 2 >= 0x80000000ull) return hipErrorInvalidValue;
-      a.Pc = a.P;
-      a.Qc = a.Q;
-      return launch_glds_ds(a, st);
-    }
-    if (g_cfg_override <= 0) {
-      const hipError_t e = launch_conv3x3_ws(a, mode == MODE_TRANS ? 1 : 0, st);
-      if (e != hipErrorNotSupported) return e;
-    }
-    if (a.xform) return hipErrorInvalidValue;  // the BN-apply prologue exists in the weight-stationary kernel only
-    if (mode == MODE_TRANS) {
-      if (a.P % a.stride || a.Q % a.stride) return hipErrorInvalidValue;
-      if (g_cfg_override <= 0) {
-        const hipError_t e = launch_conv3x3s2_dgrad(a, st);
-        if (e != hipErrorNotSupported) return e;
-      }
-      a.Pc = a.P / a.stride;
-      a.Qc = a.Q / a.stride;
-      return launch_glds<MODE_TRANS>(a, a.stride * a.stride, st);
-    }
+  if (a0.C % 32) return hipErrorInvalidValue;
+  ConvFwdArgs a = a0;
+  if ((size_t)a.N * a.H * a.W * a.ldx * 2 >= 0x80000000ull) return hipErrorInvalidValue;
+  if (a.wds) {  // the folded downsample exists in the implicit-GEMM forward only
+    if ((size_t)a.N * a.P * a.Q * a.ldyds * 2 >= 0x80000000ull) return hipErrorInvalidValue;
     a.Pc = a.P;
     a.Qc = a.Q;
-    return launch_glds<MODE_FWD>(a, 1, st);
+    return launch_glds_ds(a, st);
   }
-  return launch_conv_fwd_v1(a0, mode, st);
-}
-
-hipError_t launch_conv_fwd_v1(const ConvFwdArgs& a0, int mode, hipStream_t st) {
-  ConvFwdArgs a = a0;
-  int classes = 1;
+  if (g_cfg_override <= 0) {
+    const hipError_t e = launch_conv3x3_ws(a, mode == MODE_TRANS ? 1 : 0, st);
+    if (e != hipErrorNotSupported) return e;
+  }
+  if (a.xform) return hipErrorInvalidValue;  // the BN-apply prologue exists in the weight-stationary kernel only
   if (mode == MODE_TRANS) {
     if (a.P % a.stride || a.Q % a.stride) return hipErrorInvalidValue;
+    if (g_cfg_override <= 0) {
+      const hipError_t e = launch_conv3x3s2_dgrad(a, st);
+      if (e != hipErrorNotSupported) return e;
+    }
     a.Pc = a.P / a.stride;
     a.Qc = a.Q / a.stride;
-    classes = a.stride * a.stride;
-  } else {
-    a.Pc = a.P;
-    a.Qc = a.Q;
+    return launch_glds<MODE_TRANS>(a, a.stride * a.stride, st);
   }
-  if (mode == MODE_STEM) {
-    return launch_fwd_cfg<MODE_FWD, ALOAD_STEM, 128, 64, 64, 2, 2>(a, 1, st);
-  }
-  if (a.C % 32) return hipErrorInvalidValue;
-  const bool bk64 = (a.C % 64) == 0;
-  const int M = a.N * a.Pc * a.Qc * classes;
-#define SEL(MD)                                                                              \
-  if (a.Cout <= 32) {                                                                        \
-    return bk64 ? launch_fwd_cfg<MD, ALOAD_NHWC, 128, 32, 64, 4, 1>(a, classes, st)          \
-                : launch_fwd_cfg<MD, ALOAD_NHWC, 128, 32, 32, 4, 1>(a, classes, st);         \
-  } else if (a.Cout <= 64 || M < 32768) {                                                    \
-    return bk64 ? launch_fwd_cfg<MD, ALOAD_NHWC, 128, 64, 64, 2, 2>(a, classes, st)          \
-                : launch_fwd_cfg<MD, ALOAD_NHWC, 128, 64, 32, 2, 2>(a, classes, st);         \
-  } else {                                                                                   \
-    return bk64 ? launch_fwd_cfg<MD, ALOAD_NHWC, 128, 128, 64, 2, 2>(a, classes, st)         \
-                : launch_fwd_cfg<MD, ALOAD_NHWC, 128, 128, 32, 2, 2>(a, classes, st);        \
-  }
-  if (mode == MODE_FWD) { SEL(MODE_FWD) } else { SEL(MODE_TRANS) }
-#undef SEL
+  a.Pc = a.P;
+  a.Qc = a.Q;
+  return launch_glds<MODE_FWD>(a, 1, st);
 }
 
 template <int XLOAD, int BMO, int BNC, int BKP, int WM, int WN>
 static hipError_t launch_wgrad_cfg(const ConvWgradArgs& a0, hipStream_t st) {
   ConvWgradArgs a = a0;
   a.co_blocks = (a.Cout + BMO - 1) / BMO;
-  const int ccount = (XLOAD == XLOAD_STEM) ? 64 : a.C;
-  a.c_blocks = (ccount + BNC - 1) / BNC;
-  const int taps = (XLOAD == XLOAD_STEM) ? 1 : a.R * a.S;
+  a.c_blocks = (a.C + BNC - 1) / BNC;
+  const int taps = a.R * a.S;
   const int tiles = a.co_blocks * a.c_blocks * taps;
   const long long M = (long long)a.N * a.P * a.Q;
   // split-K over pixels: enough blocks to fill 256 CUs, but keep >= 1024 flop per
@@ -2597,8 +2342,8 @@ static hipError_t launch_wgrad_cfg(const ConvWgradArgs& a0, hipStream_t st) {
   if (a.slab && splits > 1) {
     SlabLayout L = {};
     L.kind = SLAB_GEMM; L.splits = (int)splits; L.blocks = tiles; L.nw = 4; L.nf = FM * FN; L.units = units;
-    L.Cout = a.Cout; L.C = (XLOAD == XLOAD_STEM) ? 0 : a.C; L.Krow = (XLOAD == XLOAD_STEM) ? 64 : a.R * a.S * a.C;
-    L.cmax = ccount; L.co_blocks = a.co_blocks; L.c_blocks = a.c_blocks;
+    L.Cout = a.Cout; L.C = a.C; L.Krow = a.R * a.S * a.C;
+    L.cmax = a.C; L.co_blocks = a.co_blocks; L.c_blocks = a.c_blocks;
     L.bmo = BMO; L.bnc = BNC; L.wm = WM; L.wn = WN; L.fn = FN;
     g_pending = PendingReduce{a.slab, a.dw, L};
   }
@@ -2835,10 +2580,8 @@ hipError_t launch_convt_wgrad(const ConvWgradArgs& a0, hipStream_t st) {
   return launch_wgrad_cfg<XLOAD_SHUF, 32, 32, 64, 2, 2>(a, st);
 }
 
-// UNET_NO_S2WG=1: stride-2 weight gradients on the implicit GEMM (A/B)
 bool wgrad_s2_fold_ok(const ConvWgradArgs& a) {
-  static const bool s2wg = std::getenv("UNET_NO_S2WG") == nullptr;
-  return s2wg && a.R == 3 && a.S == 3 && a.stride == 2 && a.pad == 1 && a.C % 32 == 0 &&
+  return a.R == 3 && a.S == 3 && a.stride == 2 && a.pad == 1 && a.C % 32 == 0 &&
          a.Cout % 64 == 0 && a.H == 2 * a.P && a.W == 2 * a.Q && a.Q % 16 == 0 && a.P % 8 == 0 &&
          (!a.dy2 || a.lddy2 % 8 == 0) && a.lddy % 8 == 0 && a.ldx % 8 == 0 &&
          (size_t)a.N * a.H * a.W * a.ldx * 2 < 0x80000000ull &&
@@ -2847,8 +2590,7 @@ bool wgrad_s2_fold_ok(const ConvWgradArgs& a) {
 
 hipError_t launch_conv_wgrad(const ConvWgradArgs& a0, int stem, hipStream_t st) {
   const ConvWgradArgs& a = a0;
-  if (stem)
-    return a.Cout % 64 == 0 ? launch_stem_wgrad(a, st) : launch_wgrad_cfg<XLOAD_STEM, 64, 64, 64, 2, 2>(a, st);
+  if (stem) return launch_stem_wgrad(a, st);  // 64-channel output groups; refuses any other width
   if (a.R == 3 && a.S == 3 && a.stride == 1 && a.pad == 1 && a.C % 32 == 0 && a.P == a.H &&
       a.Q == a.W && (size_t)a.N * a.H * a.W * a.ldx * 2 < 0x80000000ull &&
       (size_t)a.N * a.P * a.Q * a.lddy * 2 < 0x80000000ull) {

@@ -7,7 +7,6 @@
 // per thread (each thread owns one 8-channel chunk for its whole pixel loop),
 // folded through LDS once per block and published with fp64 atomics.
 #include <algorithm>
-#include <cstdlib>
 
 #include "common.h"
 #include "kernels.h"
@@ -21,7 +20,7 @@ namespace unet {
 // grid leaves the other CU slots to them (A/B on one box: bn_bwd 0.85 -> 0.81
 // ms, 2445 -> 2466 img/s; 128 and 192 were slower, 512 was best before the
 // reductions were merged)
-static int g_apply_cap = std::getenv("UNET_APPLY_CAP") ? std::atoi(std::getenv("UNET_APPLY_CAP")) : 256;
+constexpr int kApplyCap = 256;
 
 static inline int grid_for(int64_t work, int per_block, int cap = 2048) {
   int64_t g = (work + per_block - 1) / per_block;
@@ -146,11 +145,11 @@ static inline dim3 chunk_block(int C) {
 }
 
 // grid of the grouped BN kernels: x = pixel blocks (kBnPPT pixels per thread
-// per pass, capped so that x * groups <= g_apply_cap), y = channel groups
+// per pass, capped so that x * groups <= kApplyCap), y = channel groups
 static inline dim3 bn_grid(int64_t npix, int C) {
   const int CG = bn_group(C), groups = C / CG;
   const int rows = 256 / (CG / 8);
-  const int cap = g_apply_cap / groups > 0 ? g_apply_cap / groups : 1;
+  const int cap = kApplyCap / groups > 0 ? kApplyCap / groups : 1;
   return dim3(grid_for(npix, rows * kBnPPT, cap), groups);
 }
 
@@ -701,15 +700,15 @@ hipError_t launch_bn_relu_maxpool_fwd(const MaxPoolArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-// blocks of the maxpool backward (tuning; its fused BN-backward sums end in
+// blocks of the maxpool backward (512 / 1024 measured the same; its fused BN-backward sums end in
 // fp64 replica atomics, blocks / kStatRep per address)
-static int g_mp_blocks = std::getenv("UNET_MP_BLOCKS") ? std::atoi(std::getenv("UNET_MP_BLOCKS")) : 2048;
+constexpr int kMpBlocks = 2048;
 
 hipError_t launch_maxpool_bwd(const MaxPoolArgs& a, hipStream_t st) {
   if (a.C % 8 || 256 % (a.C / 8)) return hipErrorInvalidValue;
   if (a.bb.sums && a.bb.y2) return hipErrorInvalidValue;
   const int nrows = a.N * a.H;
-  const int rpb = rows_per_block(nrows, g_mp_blocks);
+  const int rpb = rows_per_block(nrows, kMpBlocks);
   hipLaunchKernelGGL(maxpool_bwd_kernel, dim3((nrows + rpb - 1) / rpb), dim3(256), 0, st, a, rpb);
   return hipGetLastError();
 }
@@ -1502,14 +1501,14 @@ __global__ void __launch_bounds__(256) channel_sum_kernel(const bf16_t* x, int l
   }
 }
 
-// grid cap of the channel sums (tuning): each fp64 replica address takes
+// grid cap of the channel sums (256 measured the same): each fp64 replica address takes
 // blocks / kStatRep atomics
-static int g_chsum_cap = std::getenv("UNET_CHSUM_CAP") ? std::atoi(std::getenv("UNET_CHSUM_CAP")) : 2048;
+constexpr int kChsumCap = 2048;
 
 hipError_t launch_channel_sum(const bf16_t* x, int ldx, int64_t npix, int C, double* acc, hipStream_t st) {
   if (C % 8 || C / 8 > 256) return hipErrorInvalidValue;
   const int CC = C / 8, rows = 256 / CC;
-  hipLaunchKernelGGL(channel_sum_kernel, dim3(grid_for(npix, rows * 8, g_chsum_cap)), dim3(rows * CC),
+  hipLaunchKernelGGL(channel_sum_kernel, dim3(grid_for(npix, rows * 8, kChsumCap)), dim3(rows * CC),
                      (size_t)rows * C * sizeof(float), st, x, ldx, npix, C, acc);
   return hipGetLastError();
 }

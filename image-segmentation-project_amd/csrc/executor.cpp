@@ -90,7 +90,7 @@ struct Block {
   int conv3 = -1, bn3 = -1;             // bottleneck only
   Act in, y1, h, y2, yds, out;
   Act h2, y3;                           // bottleneck: relu(bn2(y2)), conv3 output
-  Act d_out, dy1, dh, dy2, dyds, dres;  // grads
+  Act d_out, dy1, dh, dy2, dyds;        // grads
   Act dh2, dy3, dds;                    // bottleneck: grads of h2 / y3, downsample dgrad (then added)
   Act d_in;                             // == previous block's d_out (or dP0)
   Act skip_add;                         // skip-concat gradient slice for the input (or empty)
@@ -143,7 +143,7 @@ struct unet_plan {
   std::vector<Dec> decs;      // decoder4..decoder1 (index 0 = level 4)
   std::vector<Att> atts;      // attention of decoder level (same index), when cfg.attention
   int stem_conv, stem_bn, up0_w, up0_b, fin_w, fin_b;
-  Act x1, y0, p0, d_x1, d_y0, d_p0;
+  Act x1, y0, p0, d_x1, d_p0;
   size_t pidx = 0;
   size_t ws_bytes = 0;
   size_t zero_fwd_off = 0, zero_fwd_bytes = 0;
@@ -176,37 +176,23 @@ struct unet_plan {
   int tim_n = 0;
   bool tim_on = false;
   std::vector<std::string> tim_names;
-  // BN-backward reductions fused into the producing conv dgrad (UNET_NO_BWD_FUSE=1: off, A/B only)
-  bool fuse_bwd = std::getenv("UNET_NO_BWD_FUSE") == nullptr;
-  // eval forward: BN folded into the conv epilogues (UNET_NO_EVAL_FOLD=1: separate BN passes, A/B only)
+  // The switches below are read when the plan is created; the tests set them
+  // to compare a fused path with its separate-pass counterpart.
+  // eval forward: BN folded into the conv epilogues (UNET_NO_EVAL_FOLD=1: separate BN passes)
   bool eval_fold = std::getenv("UNET_NO_EVAL_FOLD") == nullptr;
-  // stem BN-backward apply fused into the stem weight gradient's dY load
-  // (UNET_NO_STEM_FUSE=1: separate apply pass writing dY, A/B only)
-  bool stem_bn_fuse = std::getenv("UNET_NO_STEM_FUSE") == nullptr;
   // BN1 + ReLU of a block / decoder level applied in the staging of the next
   // (weight-stationary) conv, which also stores the activation: no bn_apply
-  // pass (UNET_NO_BN_XFORM=1: separate pass, A/B only)
+  // pass (UNET_NO_BN_XFORM=1: separate pass)
   bool bn_xform = std::getenv("UNET_NO_BN_XFORM") == nullptr;
-  // BasicBlock downsample (1x1 / s2) weight gradient folded into the conv1
-  // (3x3 / s2) halo weight gradient (UNET_NO_DS_FOLD=1: separate launch, A/B)
-  bool ds_wgrad_fold = std::getenv("UNET_NO_DS_FOLD") == nullptr;
   // training: decoder1's last BN + ReLU formed inside the head's two passes
   // from the raw conv output (no bn_apply pass, decoder1's activation never
-  // stored; plain U-Net with the fused BN backward only).  UNET_NO_HEAD_BN_FOLD=1:
-  // separate pass (A/B only)
+  // stored; plain U-Net only).  UNET_NO_HEAD_BN_FOLD=1: separate pass
   bool head_bn_fold = std::getenv("UNET_NO_HEAD_BN_FOLD") == nullptr;
-  // single-stream backward: a weight gradient's split-K reduction rides in the
-  // next BN-backward apply launch (UNET_NO_MERGE_REDUCE=1: separate launches)
-  bool merge_reduce = std::getenv("UNET_NO_MERGE_REDUCE") == nullptr;
-  // 3x3 / s1 weight gradients of a gradient bucket collected and run as ONE
-  // batched stream-K launch at the bucket boundary (wgrad3x3_batch_kernel):
-  // no per-layer split-K slab round trip.  UNET_WG_BATCH=0: one launch per layer (A/B)
-  bool wg_batch = !(std::getenv("UNET_WG_BATCH") && std::atoi(std::getenv("UNET_WG_BATCH")) == 0);
   // the stem by recompute (stem_rc.hip): the raw 7x7 conv output y0 is never
   // stored; statistics pass + act/pool pass forward, one pass for the maxpool
   // backward, the stem BN backward and the stem weight gradient.  Shapes with
   // stem rows over 256 pixels (HiRes) keep the stored-y0 path.  UNET_STEM_RC=0:
-  // stored-y0 path everywhere (A/B); UNET_STEM_KEEP=1: y0 and dZ are stored
+  // stored-y0 path everywhere; UNET_STEM_KEEP=1: y0 and dZ are stored
   // too (tests of the intermediates)
   bool stem_rc = !(std::getenv("UNET_STEM_RC") && std::atoi(std::getenv("UNET_STEM_RC")) == 0);
   bool stem_keep = std::getenv("UNET_STEM_KEEP") && std::atoi(std::getenv("UNET_STEM_KEEP")) != 0;
@@ -526,8 +512,7 @@ static int build_plan(unet_plan* p) {
   p->y0 = act(A, N, H2, W2, c0);
   p->p0 = act(A, N, H4, W4, c0);
   p->pidx = A.take((size_t)N * H4 * W4 * c0);
-  p->stem_rc = p->stem_rc && p->fuse_bwd && p->stem_bn_fuse && stem_rc_ok(c0, H2, W2) && H2 == 2 * H4 &&
-               W2 == 2 * W4 && H == 2 * H2 && W == 2 * W2;
+  p->stem_rc = p->stem_rc && stem_rc_ok(c0, H2, W2) && H2 == 2 * H4 && W2 == 2 * W4 && H == 2 * H2 && W == 2 * W2;
   if (p->stem_rc) {
     p->stem_part = A.take(stem_rc_part_bytes(N, H2, W2, c0));
     p->stem_tot = A.take(stem_rc_tot_bytes(c0));
@@ -706,7 +691,6 @@ static int build_plan(unet_plan* p) {
     }
     const Act& o = b.out;
     if (b.ds >= 0) b.dyds = act(A, N, o.H, o.W, o.C);
-    else b.dres = act(A, N, o.H, o.W, o.C);
   }
   // block output grads: last encoder block's d_out = decoder-4's d_up_in
   const int nb = (int)p->blocks.size();
@@ -728,13 +712,11 @@ static int build_plan(unet_plan* p) {
     }
   }
   p->d_x1 = act(A, N, H2, W2, c0);
-  p->d_y0 = act(A, N, H2, W2, c0);
   p->ws_bytes = A.top;
 
   {
     const int hc = p->decs[3].out.C;
-    p->head_bn_fold = p->head_bn_fold && p->fuse_bwd && p->atts.empty() && (hc == 32 || hc == 64) &&
-                      p->decs[3].y2.C == hc;
+    p->head_bn_fold = p->head_bn_fold && p->atts.empty() && (hc == 32 || hc == 64) && p->decs[3].y2.C == hc;
   }
 
   // named views for tests: forward activations and their gradients
@@ -744,7 +726,6 @@ static int build_plan(unet_plan* p) {
   nm.push_back({"x1", p->x1}); nm.push_back({"p0", p->p0});
   if (y0_stored) nm.push_back({"d.x1", p->d_x1});
   nm.push_back({"d.p0", p->d_p0});
-  if (!(p->fuse_bwd && p->stem_bn_fuse) && !p->stem_rc) nm.push_back({"d.y0", p->d_y0});  // else never stored
   {
     int bi = 0;
     for (int s = 0; s < 4; ++s)
@@ -1129,15 +1110,13 @@ int wgrad_and_reduce(const Ctx& x, ConvWgradArgs& a, int mode, const std::string
     else CK(launch_conv_wgrad(a, mode, x.st));
   }
   if (!wgrad_pending()) return 0;
-  if (p->merge_reduce) {
-    // one reduction at most waits for an apply launch; an older one runs now
-    // (it reads the other slab, so the order against this wgrad is free)
-    if (wgrad_deferred()) {
-      ProfScope pr(p, x.st, "wgrad_reduce (deferred)", 0);
-      CK(launch_wgrad_flush(x.st));
-    }
-    if (wgrad_defer()) return 0;
+  // one reduction at most waits for an apply launch; an older one runs now
+  // (it reads the other slab, so the order against this wgrad is free)
+  if (wgrad_deferred()) {
+    ProfScope pr(p, x.st, "wgrad_reduce (deferred)", 0);
+    CK(launch_wgrad_flush(x.st));
   }
+  if (wgrad_defer()) return 0;
   {
     ProfScope pr(p, x.st, "wgrad_reduce " + name, 0);
     CK(launch_wgrad_finish(x.st));
@@ -1175,7 +1154,7 @@ int conv_wgrad(const Ctx& x, int ci, const Act& dy, const Act& in, int ds = -1, 
     fl += conv_flops(x.p, dv, *dyds);
     name += " +ds";
   }
-  if (x.p->wg_batch && wgrad_batch_ok(a)) {  // runs in the bucket's batch (flush_wgrad_batch)
+  if (wgrad_batch_ok(a)) {  // runs in the bucket's batch (flush_wgrad_batch)
     x.p->wgb.push_back(a);
     x.p->wgb_names.push_back(name);
     x.p->wgb_flops += fl;
@@ -1284,7 +1263,7 @@ int bn_apply(const Ctx& x, int bi, const Act& y, const Act& out, int res_mode, c
 
 // BN(+ReLU) backward argument block for out = relu(bn(y) [+ bn2(y2) | + res]).
 BnBwdArgs bwd_args(const Ctx& x, int bi, const Act& dout, const Act& out, const Act& y, const Act& dy,
-                   int bi2, const Act* y2, const Act* dy2, const Act* dres, float* grads) {
+                   int bi2, const Act* y2, const Act* dy2, float* grads) {
   BnBwdArgs a = {};
   const Bn& b = x.p->bns[bi];
   a.da = x.A(dout); a.ldda = dout.ld;
@@ -1304,21 +1283,15 @@ BnBwdArgs bwd_args(const Ctx& x, int bi, const Act& dout, const Act& out, const 
     a.dgamma2 = grads + x.p->params[b2.gamma].flat;
     a.dbeta2 = grads + x.p->params[b2.beta].flat;
   }
-  if (dres) { a.dres = x.A(*dres); a.lddres = dres->ld; }
   a.npix = (int64_t)x.p->cfg.N * y.H * y.W; a.C = y.C; a.relu = 1;
   return a;
 }
 
-// fused: the producer of dA already stored dZ (in dA's buffer, which then also
-// serves as the identity-residual gradient) and reduced it; only apply runs.
-int bn_backward(const Ctx& x, int bi, BnBwdArgs a, bool fused) {
+// The producer of dA already stored dZ (in dA's buffer, which then also serves
+// as the identity-residual gradient) and reduced it; only the apply runs.
+int bn_backward(const Ctx& x, int bi, BnBwdArgs a) {
   ProfScope ps(x.p, x.st, "bn_bwd " + pname(x, x.p->bns[bi].gamma), 0);
-  if (fused) {
-    a.relu = 0;
-    a.dres = nullptr;
-  } else {
-    CK(launch_bn_bwd_reduce(a, x.st));
-  }
+  a.relu = 0;
   ReduceTail r;
   if (wgrad_deferred() && wgrad_take_deferred(&r)) {
     const hipError_t e = launch_bn_bwd_apply_reduce(a, r, x.st);
@@ -1719,9 +1692,9 @@ static int run_backward(unet_plan* p, const float* image, const float* dlogits, 
     h.gwf = grads + p->params[p->fin_w].flat; h.gbf = grads + p->params[p->fin_b].flat;
     h.N = N; h.H = o.H; h.W = o.W; h.Cin = o.C; h.Co = (int)p->params[p->up0_b].numel;
     h.K = p->cfg.n_classes;
-    if (p->fuse_bwd && !att) {  // the head produces dA of decoder1's last BN: reduce it here
+    if (!att) {  // the head produces dA of decoder1's last BN: reduce it here
       const Dec& d = p->decs[3];
-      h.bb = bwd_args(x, d.bn2, d.d_out, d.out, d.y2, d.dy2, -1, nullptr, nullptr, nullptr, grads);
+      h.bb = bwd_args(x, d.bn2, d.d_out, d.out, d.y2, d.dy2, -1, nullptr, nullptr, grads);
       if (p->head_bn_fold) {  // the forward never stored act: recomputed from y2 (same bits)
         h.x = x.A(d.y2); h.ldx = d.y2.ld;
         h.bb.act = nullptr;
@@ -1735,19 +1708,18 @@ static int run_backward(unet_plan* p, const float* image, const float* dlogits, 
   }
   // BN-backward reductions are fused into the conv dgrad that produces each
   // BN's dA (all but decoder1's second BN, fed by the head, and the stem BN).
-  const bool fz = p->fuse_bwd;
   const int nb = (int)p->blocks.size();
   auto dec_bn1 = [&](int l) {
     Dec& d = p->decs[l];
-    return bwd_args(x, d.bn1, d.dh, d.h, d.y1, d.dy1, -1, nullptr, nullptr, nullptr, grads);
+    return bwd_args(x, d.bn1, d.dh, d.h, d.y1, d.dy1, -1, nullptr, nullptr, grads);
   };
   auto dec_bn2 = [&](int l) {
     Dec& d = p->decs[l];
-    return bwd_args(x, d.bn2, d.d_out, d.out, d.y2, d.dy2, -1, nullptr, nullptr, nullptr, grads);
+    return bwd_args(x, d.bn2, d.d_out, d.out, d.y2, d.dy2, -1, nullptr, nullptr, grads);
   };
   auto blk_bn1 = [&](int i) {
     Block& b = p->blocks[i];
-    return bwd_args(x, b.bn1, b.dh, b.h, b.y1, b.dy1, -1, nullptr, nullptr, nullptr, grads);
+    return bwd_args(x, b.bn1, b.dh, b.h, b.y1, b.dy1, -1, nullptr, nullptr, grads);
   };
   // the block's last BN (bn2 of a BasicBlock, bn3 of a Bottleneck), paired
   // with the downsample BN when the block has one
@@ -1756,8 +1728,8 @@ static int run_backward(unet_plan* p, const float* image, const float* dlogits, 
     const int bl = b.last_bn();
     const Act& yl = b.last_y();
     const Act& dyl = b.last_dy();
-    if (b.ds >= 0) return bwd_args(x, bl, b.d_out, b.out, yl, dyl, b.dsbn, &b.yds, &b.dyds, nullptr, grads);
-    return bwd_args(x, bl, b.d_out, b.out, yl, dyl, -1, nullptr, nullptr, &b.dres, grads);
+    if (b.ds >= 0) return bwd_args(x, bl, b.d_out, b.out, yl, dyl, b.dsbn, &b.yds, &b.dyds, grads);
+    return bwd_args(x, bl, b.d_out, b.out, yl, dyl, -1, nullptr, nullptr, grads);
   };
   // decoder1 .. decoder4 (+ their up-convs)
   for (int l = 3; l >= 0; --l) {
@@ -1769,13 +1741,14 @@ static int run_backward(unet_plan* p, const float* image, const float* dlogits, 
         ProfScope ps(p, st, "ch_att_bwd", 0);
         for (int pass = 3; pass < 6; ++pass) CK(launch_ch_att(c, pass, st));
       }
-      RUN(bn_backward(x, d.bn2, c.bb, true));
+      RUN(bn_backward(x, d.bn2, c.bb));
+    } else {
+      RUN(bn_backward(x, d.bn2, dec_bn2(l)));
     }
-    if (!att) RUN(bn_backward(x, d.bn2, dec_bn2(l), fz));
     RUN(conv_wgrad(x, d.conv2, d.dy2, d.h));
     const BnBwdArgs f1 = dec_bn1(l);
-    RUN(conv_dgrad(x, d.conv2, d.dy2, d.dh, nullptr, fz ? &f1 : nullptr));
-    RUN(bn_backward(x, d.bn1, f1, fz));
+    RUN(conv_dgrad(x, d.conv2, d.dy2, d.dh, nullptr, &f1));
+    RUN(bn_backward(x, d.bn1, f1));
     RUN(conv_wgrad(x, d.conv1, d.dy1, d.cat));
     RUN(conv_dgrad(x, d.conv1, d.dy1, d.dcat, nullptr, nullptr, -1, nullptr, d.split ? &d.dcat_up : nullptr));
     // (decoder conv bias gradients: exactly 0, written by bucket 0's unpack)
@@ -1786,13 +1759,13 @@ static int run_backward(unet_plan* p, const float* image, const float* dlogits, 
       AttGateArgs a = gate_args(x, l, grads);
       // relu(BN_g + BN_x) backward: its reduction runs inside the gate's apply
       // pass (which produces dA and already reads the relu output)
-      a.bb = bwd_args(x, t.bng, t.dS, t.s, t.g1, t.dg1, t.bnx, &t.xa, &t.dxa, nullptr, grads);
+      a.bb = bwd_args(x, t.bng, t.dS, t.s, t.g1, t.dg1, t.bnx, &t.xa, &t.dxa, grads);
       {
         ProfScope ps(p, st, "att_gate_bwd", 0);
         CK(launch_att_gate(a, 2, st));
         CK(launch_att_gate(a, 3, st));
       }
-      RUN(bn_backward(x, t.bng, a.bb, true));
+      RUN(bn_backward(x, t.bng, a.bb));
       RUN(conv_wgrad(x, t.wg, t.dg1, d.up_out));
       RUN(conv_wgrad(x, t.wx, t.dxa, t.x));
       RUN(conv_dgrad(x, t.wg, t.dg1, t.du, &d.dcat_up));
@@ -1805,7 +1778,7 @@ static int run_backward(unet_plan* p, const float* image, const float* dlogits, 
     const BnBwdArgs fu = l > 0 ? dec_bn2(l - 1) : blk_bn2(nb - 1);
     // with attention the up-conv input of levels 3..1 is the channel-gated
     // output: its gradient is not dA of a BN
-    const bool fuse_up = fz && (l == 0 || !att);
+    const bool fuse_up = l == 0 || !att;
     // the bias gradient (replicas -> fp32 in bucket 0's unpack launch, UP_D2F)
     // rides in the data-gradient pass when its kernel covers the shape
     bool bias_fused = false;
@@ -1822,21 +1795,22 @@ static int run_backward(unet_plan* p, const float* image, const float* dlogits, 
   // encoder blocks, deepest first
   for (int i = nb - 1; i >= 0; --i) {
     Block& b = p->blocks[i];
+    // the last writer of d_in produces dA of the previous block's last BN
+    BnBwdArgs fp = {};
+    const BnBwdArgs* fprev = nullptr;
+    if (i > 0) { fp = blk_bn2(i - 1); fprev = &fp; }
+    RUN(bn_backward(x, b.last_bn(), blk_bn2(i)));  // dY of the last conv (+ dY of the downsample BN)
     if (b.bottleneck()) {
-      RUN(bn_backward(x, b.bn3, blk_bn2(i), fz));  // dY3 (+ dY of the downsample BN)
       RUN(conv_wgrad(x, b.conv3, b.dy3, b.h2));
       if (b.ds >= 0) RUN(conv_wgrad(x, b.ds, b.dyds, b.in));
-      const BnBwdArgs f2 = bwd_args(x, b.bn2, b.dh2, b.h2, b.y2, b.dy2, -1, nullptr, nullptr, nullptr, grads);
-      RUN(conv_dgrad(x, b.conv3, b.dy3, b.dh2, nullptr, fz ? &f2 : nullptr));
-      RUN(bn_backward(x, b.bn2, f2, fz));
+      const BnBwdArgs f2 = bwd_args(x, b.bn2, b.dh2, b.h2, b.y2, b.dy2, -1, nullptr, nullptr, grads);
+      RUN(conv_dgrad(x, b.conv3, b.dy3, b.dh2, nullptr, &f2));
+      RUN(bn_backward(x, b.bn2, f2));
       RUN(conv_wgrad(x, b.conv2, b.dy2, b.h));
       const BnBwdArgs f1 = blk_bn1(i);
-      RUN(conv_dgrad(x, b.conv2, b.dy2, b.dh, nullptr, fz ? &f1 : nullptr));
-      RUN(bn_backward(x, b.bn1, f1, fz));
+      RUN(conv_dgrad(x, b.conv2, b.dy2, b.dh, nullptr, &f1));
+      RUN(bn_backward(x, b.bn1, f1));
       RUN(conv_wgrad(x, b.conv1, b.dy1, b.in));
-      BnBwdArgs fp = {};
-      const BnBwdArgs* fprev = nullptr;
-      if (fz && i > 0) { fp = blk_bn2(i - 1); fprev = &fp; }
       if (b.ds >= 0) {
         // downsample (1x1 / stride) data gradient (+ the skip-concat gradient
         // of the input), then conv1's (1x1) added to it with the previous
@@ -1844,33 +1818,22 @@ static int run_backward(unet_plan* p, const float* image, const float* dlogits, 
         RUN(conv_dgrad(x, b.ds, b.dyds, b.dds, b.skip_add.ld ? &b.skip_add : nullptr));
         RUN(conv_dgrad(x, b.conv1, b.dy1, b.d_in, &b.dds, fprev));
       } else {
-        RUN(conv_dgrad(x, b.conv1, b.dy1, b.d_in, fz ? &b.d_out : &b.dres, fprev));
+        RUN(conv_dgrad(x, b.conv1, b.dy1, b.d_in, &b.d_out, fprev));  // identity path: d_out holds dZ of bn3
       }
-      if (i == 13 || i == 7) {
-        const int bk = i == 13 ? 1 : 2;
-        RUN(unpack_bucket(x, bk, grads));
-        if (p->nevents) CK(hipEventRecord(p->events[bk], x.st));
-      }
-      continue;
-    }
-    RUN(bn_backward(x, b.bn2, blk_bn2(i), fz));
-    RUN(conv_wgrad(x, b.conv2, b.dy2, b.h));
-    const bool dsfold = p->ds_wgrad_fold && ds_fold_ok(x, b);
-    if (b.ds >= 0 && !dsfold) RUN(conv_wgrad(x, b.ds, b.dyds, b.in));
-    const BnBwdArgs f1 = blk_bn1(i);
-    RUN(conv_dgrad(x, b.conv2, b.dy2, b.dh, nullptr, fz ? &f1 : nullptr));
-    RUN(bn_backward(x, b.bn1, f1, fz));
-    RUN(conv_wgrad(x, b.conv1, b.dy1, b.in, dsfold ? b.ds : -1, &b.dyds));
-    // the last writer of d_in produces dA of the previous block's bn2
-    BnBwdArgs fp = {};
-    const BnBwdArgs* fprev = nullptr;
-    if (fz && i > 0) { fp = blk_bn2(i - 1); fprev = &fp; }
-    if (b.ds >= 0) {
-      // conv1 (3x3/s2) and downsample (1x1/s2) data gradients in one launch
-      RUN(conv_dgrad(x, b.conv1, b.dy1, b.d_in, b.skip_add.ld ? &b.skip_add : nullptr, fprev, b.ds, &b.dyds));
     } else {
-      // identity path: dZ of bn2 (held in d_out when fused)
-      RUN(conv_dgrad(x, b.conv1, b.dy1, b.d_in, fz ? &b.d_out : &b.dres, fprev));
+      RUN(conv_wgrad(x, b.conv2, b.dy2, b.h));
+      const bool dsfold = ds_fold_ok(x, b);
+      if (b.ds >= 0 && !dsfold) RUN(conv_wgrad(x, b.ds, b.dyds, b.in));
+      const BnBwdArgs f1 = blk_bn1(i);
+      RUN(conv_dgrad(x, b.conv2, b.dy2, b.dh, nullptr, &f1));
+      RUN(bn_backward(x, b.bn1, f1));
+      RUN(conv_wgrad(x, b.conv1, b.dy1, b.in, dsfold ? b.ds : -1, &b.dyds));
+      if (b.ds >= 0) {
+        // conv1 (3x3/s2) and downsample (1x1/s2) data gradients in one launch
+        RUN(conv_dgrad(x, b.conv1, b.dy1, b.d_in, b.skip_add.ld ? &b.skip_add : nullptr, fprev, b.ds, &b.dyds));
+      } else {
+        RUN(conv_dgrad(x, b.conv1, b.dy1, b.d_in, &b.d_out, fprev));  // identity path: d_out holds dZ of bn2
+      }
     }
     // bucket boundaries: enc4 done at i == 13, enc3 at i == 7
     if (i == 13 || i == 7) {
@@ -1885,13 +1848,14 @@ static int run_backward(unet_plan* p, const float* image, const float* dlogits, 
     RUN(unpack_bucket(x, bk, grads));
     if (p->nevents) CK(hipEventRecord(p->events[bk], x.st));
   }
-  // maxpool + stem
-  if (p->stem_rc && fz) {
+  // maxpool + stem.  dY of the stem is never stored: both paths form it from
+  // dZ and y inside the stem weight gradient
+  const Act skip = att ? p->atts[3].dskip : slice(p->decs[3].dcat, 0, p->x1.C);
+  BnBwdArgs sb = bwd_args(x, p->stem_bn, p->d_x1, p->x1, p->y0, Act(), -1, nullptr, nullptr, grads);
+  sb.dy = nullptr;
+  if (p->stem_rc) {
     // one pass: maxpool backward, stem BN backward, stem weight gradient
     StemRcArgs s = stem_rc_args(x, image);
-    const Act skip = att ? p->atts[3].dskip : slice(p->decs[3].dcat, 0, p->x1.C);
-    const BnBwdArgs sb = bwd_args(x, p->stem_bn, p->d_x1, p->x1, p->y0, p->d_y0, -1, nullptr, nullptr, nullptr,
-                                  grads);
     s.dpool = x.A(p->d_p0); s.lddpool = p->d_p0.ld;
     s.add = x.A(skip); s.ldadd = skip.ld;
     s.mean = sb.mean; s.invstd = sb.invstd;
@@ -1916,25 +1880,17 @@ static int run_backward(unet_plan* p, const float* image, const float* dlogits, 
   } else {
     MaxPoolArgs m = {};
     m.dy = x.A(p->d_p0); m.lddy = p->d_p0.ld; m.idx = x.W<uint8_t>(p->pidx);
-    const Act skip = att ? p->atts[3].dskip : slice(p->decs[3].dcat, 0, p->x1.C);
     m.add = x.A(skip); m.ldadd = skip.ld;
     m.dx = x.A(p->d_x1); m.lddx = p->d_x1.ld;
     m.N = N; m.H = p->x1.H; m.W = p->x1.W; m.C = p->x1.C; m.P = p->p0.H; m.Q = p->p0.W;
-    // the maxpool backward produces dA of the stem BN: fuse its reduction
-    const BnBwdArgs sb = bwd_args(x, p->stem_bn, p->d_x1, p->x1, p->y0, p->d_y0, -1, nullptr, nullptr, nullptr,
-                                  grads);
-    if (fz) m.bb = sb;
+    m.bb = sb;  // the maxpool backward produces dA of the stem BN: its reduction rides here
     {
       ProfScope ps(p, st, "maxpool_bwd", 0);
       CK(launch_maxpool_bwd(m, st));
     }
     const Conv& cv = p->convs[p->stem_conv];
-    // fused: the stem wgrad forms dY from dZ and y itself (no apply pass, dY never stored)
-    const bool stem_fuse = fz && p->stem_bn_fuse && cv.Co % 64 == 0;
-    if (!stem_fuse) RUN(bn_backward(x, p->stem_bn, sb, fz));
     ConvWgradArgs a = {};
-    a.dy = x.A(p->d_y0); a.lddy = p->d_y0.ld;
-    if (stem_fuse) { a.bn = sb; a.bn_fuse = 1; }
+    a.bn = sb; a.bn_fuse = 1;
     a.dw = x.W<float>(cv.wacc);
     a.N = N; a.H = p->cfg.H; a.W = p->cfg.W; a.C = 1;
     a.P = p->y0.H; a.Q = p->y0.W; a.Cout = cv.Co;
@@ -2265,6 +2221,13 @@ int unet_grad_from_bf16(const void* src, float* dst, int64_t n, float scale, hip
   return 0;
 }
 
+// the stem kernels work on 64-channel output groups (unet_conv_fwd mode 2, unet_conv_wgrad* stem = 1)
+static bool stem_width_ok(const char* fn, int Cout) {
+  if (Cout > 0 && Cout % 64 == 0) return true;
+  set_err(std::string(fn) + ": the stem needs Cout % 64 == 0");
+  return false;
+}
+
 int unet_conv_fwd(const void* x, int ldx, const void* w, void* y, int ldy, const float* bias, const void* addend,
                   int ldadd, double* stats, int N, int H, int W, int C, int P, int Q, int Cout, int R, int S,
                   int stride, int pad, int mode, hipStream_t stream) {
@@ -2274,6 +2237,7 @@ int unet_conv_fwd(const void* x, int ldx, const void* w, void* y, int ldy, const
   a.N = N; a.H = H; a.W = W; a.C = C; a.P = P; a.Q = Q; a.Cout = Cout;
   a.R = R; a.S = S; a.stride = stride; a.pad = pad;
   if (mode < 0 || mode > 2) { set_err("bad mode"); return 1; }
+  if (mode == MODE_STEM && !stem_width_ok("unet_conv_fwd", Cout)) return 1;
   CK(launch_conv_fwd(a, mode, stream));
   return 0;
 }
@@ -2474,6 +2438,7 @@ int unet_conv_wgrad(const void* dy, int lddy, const void* x, int ldx, float* dw_
   a.dy = (const bf16_t*)dy; a.lddy = lddy; a.x = (const bf16_t*)x; a.ldx = ldx; a.dw = dw_acc;
   a.N = N; a.H = H; a.W = W; a.C = C; a.P = P; a.Q = Q; a.Cout = Cout;
   a.R = R; a.S = S; a.stride = stride; a.pad = pad;
+  if (stem && !stem_width_ok("unet_conv_wgrad", Cout)) return 1;
   CK(launch_conv_wgrad(a, stem, stream));
   return 0;
 }
@@ -2487,6 +2452,7 @@ int unet_conv_wgrad_slab(const void* dy, int lddy, const void* x, int ldx, float
   a.slab = (float*)slab; a.slab_bytes = (size_t)slab_bytes;
   a.N = N; a.H = H; a.W = W; a.C = C; a.P = P; a.Q = Q; a.Cout = Cout;
   a.R = R; a.S = S; a.stride = stride; a.pad = pad;
+  if (stem && !stem_width_ok("unet_conv_wgrad_slab", Cout)) return 1;
   CK(launch_conv_wgrad(a, stem, stream));
   CK(launch_wgrad_finish(stream));
   return 0;

@@ -25,11 +25,10 @@ enum { MODE_FWD = 0, MODE_TRANS = 1, MODE_STEM = 2, MODE_SHUF = 3 };
 // hit the same addresses (MI355X_MICROARCH.md, float atomics "contention");
 // readers sum the replicas.  Layout everywhere: [kStatRep][2][C].
 constexpr int kStatRep = 16;
-enum { ALOAD_NHWC = 0, ALOAD_STEM = 1 };
 // XLOAD_SHUF: ConvTranspose2d(k2,s2) weight gradient as one GEMM over the
 // INPUT pixels: dW[ci][t][co] = sum_px X[px][ci] * dY[2i + t/2, 2j + t%2][co]
 // (x = dY gathered 4 output pixels per input pixel, C = 4*Co, R = S = 1)
-enum { XLOAD_NHWC = 0, XLOAD_STEM = 1, XLOAD_SHUF = 2 };
+enum { XLOAD_NHWC = 0, XLOAD_SHUF = 2 };
 
 // BatchNorm parameters of one layer.  Training: the producer (conv epilogue)
 // only adds its per-channel sums into the replicas of `stats`; every consumer
@@ -56,7 +55,7 @@ struct BnBwdArgs {
   double* sums2;                     // [2][C] for bn2
   bf16_t* dy; int lddy;              // apply: dY out
   bf16_t* dy2; int lddy2;            // apply: dY2 out (bn2)
-  bf16_t* dres; int lddres;          // apply: dZ out (identity residual) or null
+  bf16_t* dres; int lddres;          // apply: dZ out (identity residual) or null (unet_bn_backward only)
   float* dgamma; float* dbeta;       // param grads (written by the apply's blocks bx == 0 from the sums)
   float* dgamma2; float* dbeta2;
   int64_t npix; int C; int relu;
@@ -172,7 +171,6 @@ struct ConvWgradArgs {
 bool wgrad_s2_fold_ok(const ConvWgradArgs& a);
 
 hipError_t launch_conv_fwd(const ConvFwdArgs& a, int mode, hipStream_t st);
-hipError_t launch_conv_fwd_v1(const ConvFwdArgs& a, int mode, hipStream_t st);  // register-staged
 // weight-stationary halo kernel for 3x3/s1/p1 layers with few channels
 // (conv_halo.hip); mode 0 conv, 1 dgrad.  hipErrorNotSupported if not covered.
 hipError_t launch_conv3x3_ws(const ConvFwdArgs& a, int mode, hipStream_t st);
@@ -182,7 +180,7 @@ bool conv3x3_ws_xform_ok(const ConvFwdArgs& a);
 // full-line halo kernel (conv_fl.hip) for 3x3/s1/p1 layers with C % 128 == 0,
 // Cout % 64 == 0 (P, Q multiples of 16): a.wch holds the chunk-major pack
 // (PK_CONV_FWD_CH / PK_CONV_DGRAD_CH); mode 0 conv, 1 dgrad.  The plan packs
-// those convs chunk-major exactly when conv3x3_fl_shape holds (UNET_NO_FL=1: never)
+// those convs chunk-major exactly when conv3x3_fl_shape holds
 bool conv3x3_fl_shape(int N, int C, int Cout, int P, int Q);
 // the geometry alone (what launch_conv3x3_fl accepts; the single-op C ABI may
 // launch shapes that do not fill the chip)
@@ -210,7 +208,7 @@ hipError_t launch_conv1x1(const ConvFwdArgs& a, int mode, hipStream_t st);
 // forward's launch (geometry, tile choice)?  false: launch them separately
 bool conv_fwd_ds_ok(const ConvFwdArgs& a);
 // weight-stationary full-line conv for C == 64 (conv_fl.hip), standard weight
-// pack; launch_conv3x3_ws uses it where conv3x3_ws2_ok holds (UNET_NO_WS2=1: never)
+// pack; launch_conv3x3_ws uses it where conv3x3_ws2_ok holds
 bool conv3x3_ws2_ok(const ConvFwdArgs& a, bool flip);
 hipError_t launch_conv3x3_ws2(const ConvFwdArgs& a, int mode, hipStream_t st);
 // 3x3 / stride-2 / pad-1 data gradient by parity class on a shared dY halo
@@ -302,6 +300,8 @@ struct BnApplyArgs {
 };
 hipError_t launch_bn_apply(const BnApplyArgs& a, hipStream_t st);
 
+// the reduction as a pass of its own: the single-op unet_bn_backward only (in a
+// plan every producer of a BN's dA reduces in its epilogue)
 hipError_t launch_bn_bwd_reduce(const BnBwdArgs& a, hipStream_t st);
 hipError_t launch_bn_bwd_apply(const BnBwdArgs& a, hipStream_t st);
 // the same with a deferred split-K reduction as trailing blocks (256-thread

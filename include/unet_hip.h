@@ -234,10 +234,14 @@ int unet_grad_from_bf16(const void* src, float* dst, int64_t n, float scale, hip
 /* ---- single ops (tests / custom graphs) ---- */
 /* mode 0: conv  y = conv(x, w) [stride, pad]           (w packed [Cout][R][S][C])
  * mode 1: transposed gather (conv dgrad / ConvTranspose2d forward)
- * mode 2: 7x7 stem on an fp32 single-channel image     (w packed [64][64]) */
+ * mode 2: 7x7 stem on an fp32 single-channel image     (w packed [64][64] per
+ *         64-channel output group; Cout % 64 == 0, any other width is refused
+ *         with a message and nothing is launched) */
 int unet_conv_fwd(const void* x, int ldx, const void* w, void* y, int ldy, const float* bias,
                   const void* addend, int ldadd, double* stats, int N, int H, int W, int C, int P,
                   int Q, int Cout, int R, int S, int stride, int pad, int mode, hipStream_t stream);
+/* stem != 0 (here and in unet_conv_wgrad_slab): the 7x7 stem's weight gradient,
+ * x the fp32 image; Cout % 64 == 0, refused like unet_conv_fwd mode 2 otherwise. */
 int unet_conv_wgrad(const void* dy, int lddy, const void* x, int ldx, float* dw_acc, int N, int H,
                     int W, int C, int P, int Q, int Cout, int R, int S, int stride, int pad, int stem,
                     hipStream_t stream);

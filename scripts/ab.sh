@@ -5,8 +5,8 @@
 # reverse order (ABBA), medians at the end.
 # A variant is  [VAR=val[,VAR=val...]][@lib.so]  ("-" or "" = defaults, the
 # in-tree libunet_hip.so); e.g.
-#   scripts/ab.sh 3 - @ab/libunet_hip_r04.so UNET_APPLY_CAP=1024
-#   BENCH_ARGS="--width 2" scripts/ab.sh 3 - UNET_NO_FL=1
+#   scripts/ab.sh 3 - @ab/libunet_hip_r04.so UNET_NO_HEAD_BN_FOLD=1
+#   BENCH_ARGS="--width 2" scripts/ab.sh 3 - UNET_STEM_RC=0
 # AB_LAYERS="<regex>": per-layer instead (scripts/layer_profile.py, HIP events
 # around every launch), printing the matching launch lines of every variant
 set -o pipefail

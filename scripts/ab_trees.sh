@@ -3,6 +3,7 @@
 # self-contained tree (its own bench.py, package and built library; e.g. an
 # earlier round's commit built under ab/<name>/): R rounds, ABBA order,
 # medians at the end.  Usage: scripts/ab_trees.sh R ab/r05
+#   BENCH_ARGS="--attention" scripts/ab_trees.sh 4 ab/parent
 set -o pipefail
 export TMPDIR=/tmp
 mkdir -p gpurun_out
@@ -11,7 +12,7 @@ out=gpurun_out/ab_trees.txt
 : > $out
 STEPS=${STEPS:-150}
 run() {  # $1 = tree
-  (cd "$1" && timeout -k 10 120 python3 bench.py --no-cpu-baseline --no-parity --steps $STEPS --warmup 20 2>/dev/null) \
+  (cd "$1" && timeout -k 10 120 python3 bench.py --no-cpu-baseline --no-parity --steps $STEPS --warmup 20 $BENCH_ARGS 2>/dev/null) \
     | grep -o '"value": [0-9.]*' | grep -o '[0-9.]*$'
 }
 for r in $(seq 1 $R); do

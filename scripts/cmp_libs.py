@@ -2,11 +2,11 @@
 runs in its own process (UNET_HIP_LIB); the logits, every parameter gradient,
 every buffer after the step (running_mean / running_var / num_batches_tracked
 of each BN) and the logits of one eval() forward of the same input after the
-step (running statistics, eval fold) are saved and compared bit for bit.  For
-refactors that must not change numerics (same summation orders, same
-expressions).
-usage: python scripts/cmp_libs.py lib_a.so lib_b.so [--batch 4] [--size 256]
-                                  [--attention] [--backbone resnet34|resnet50]"""
+step (running statistics, eval fold) are saved and compared bit for bit; each
+build's plan workspace size is printed.  For refactors that must not change
+numerics (same summation orders, same expressions).
+usage: python scripts/cmp_libs.py lib_a.so lib_b.so [--batch 4] [--size 256] [--attention]
+                                  [--backbone resnet34|resnet50] [--width 1|2] [--fp8]"""
 import argparse
 import os
 import subprocess
@@ -18,6 +18,8 @@ ap.add_argument("--batch", type=int, default=4)
 ap.add_argument("--size", type=int, default=256)
 ap.add_argument("--attention", action="store_true")
 ap.add_argument("--backbone", choices=["resnet34", "resnet50"], default="resnet34")
+ap.add_argument("--width", type=int, default=1)
+ap.add_argument("--fp8", action="store_true")
 ap.add_argument("--child", default="")
 args = ap.parse_args()
 
@@ -28,12 +30,14 @@ if args.child:
     sys.path.insert(0, ".")
     pkg = importlib.import_module("image-segmentation-project_amd")
     torch.manual_seed(0)
-    m = pkg.UNetWithBackbone(pretrained=False, backbone=args.backbone, use_attention=args.attention).cuda().train()
+    m = pkg.UNetWithBackbone(pretrained=False, backbone=args.backbone, use_attention=args.attention, width=args.width,
+                             fp8=args.fp8).cuda().train()
     xs, ms = pkg.synthetic_cells(args.batch, args.size, args.size, seed=5)
     x, y = torch.from_numpy(xs).cuda(), torch.from_numpy(ms).cuda()
     out = m(x)
     pkg.get_loss_function({"loss_fn": "bce"})(out, y).backward()
     torch.cuda.synchronize()
+    print(f"{os.environ['UNET_HIP_LIB']}: plan workspace {m._last_plan.workspace.numel()} bytes")
     res = {"logits": out.detach().cpu()}
     res.update({k: p.grad.detach().cpu() for k, p in m.named_parameters()})
     res.update({"buffer." + k: b.detach().cpu() for k, b in m.named_buffers()})
@@ -48,7 +52,8 @@ for i, lib in enumerate(args.libs):
     path = f"/tmp/cmp_libs_{i}.pt"
     env = dict(os.environ, UNET_HIP_LIB=os.path.abspath(lib))
     subprocess.run([sys.executable, __file__, *args.libs, "--batch", str(args.batch), "--size", str(args.size),
-                    "--backbone", args.backbone, *(["--attention"] if args.attention else []), "--child", path],
+                    "--backbone", args.backbone, "--width", str(args.width),
+                    *(["--attention"] if args.attention else []), *(["--fp8"] if args.fp8 else []), "--child", path],
                    env=env, check=True)
     outs.append(path)
 import torch  # noqa: E402

@@ -230,6 +230,35 @@ def test_stem_fwd_and_wgrad(L, N, H, Co, cuda):
     close(out, wref, rel=2e-3)
 
 
+def test_stem_refuses_other_widths(L, cuda):
+    """The stem kernels work on 64-channel output groups: Cout = 32 is refused by
+    the forward and by both weight-gradient entries with a message naming the
+    condition, before any launch (the outputs keep their sentinel)."""
+    N, H, Co = 1, 32, 32
+    P = H // 2
+    x = torch.zeros(N, H, H, device="cuda")
+    wp = torch.zeros(Co * 64, dtype=torch.bfloat16, device="cuda")
+    y = torch.full((N, P, P, Co), 7.0, dtype=torch.bfloat16, device="cuda")
+    dy = torch.zeros(N, P, P, Co, dtype=torch.bfloat16, device="cuda")
+    acc = torch.full((Co * 64,), 7.0, device="cuda")
+    slab = torch.full((1 << 16,), 7.0, device="cuda")
+    geom = (N, H, H, 1, P, P, Co, 7, 7, 2, 3)
+    calls = {
+        "unet_conv_fwd": lambda: L.unet_conv_fwd(x.data_ptr(), 1, wp.data_ptr(), y.data_ptr(), Co, 0, 0, 0, 0,
+                                                 *geom, 2, S()),
+        "unet_conv_wgrad": lambda: L.unet_conv_wgrad(dy.data_ptr(), Co, x.data_ptr(), 1, acc.data_ptr(), *geom, 1, S()),
+        "unet_conv_wgrad_slab": lambda: L.unet_conv_wgrad_slab(dy.data_ptr(), Co, x.data_ptr(), 1, acc.data_ptr(),
+                                                               slab.data_ptr(), slab.numel() * 4, *geom, 1, S()),
+    }
+    for name, call in calls.items():
+        rc = call()
+        torch.cuda.synchronize()
+        assert rc != 0, name
+        assert L.unet_last_error().decode() == f"{name}: the stem needs Cout % 64 == 0"
+        for out in (y, acc, slab):
+            assert bool((out.float() == 7.0).all()), name
+
+
 @pytest.mark.parametrize("C,res", [(64, 0), (32, 1), (96, 0), (512, 1)])
 def test_bn_forward_backward(L, C, res, cuda):
     """relu(bn(y) [+ r]) training forward (batch stats, running-stat update) and
