@@ -5,7 +5,8 @@ Drop-in for the hot path of SwagMag1213/image-segmentation-project
 bce/dice/combo, ``utils.calculate_metrics``, ``train.train_epoch/evaluate``),
 plus softmax losses and argmax metrics for mutually exclusive classes
 (``CrossEntropyLoss``, ``SoftmaxDiceLoss``, ``SoftmaxComboLoss``, ``confusion_matrix``)
-and tiled whole-frame inference on frames of any size (``predict``),
+and tiled whole-frame inference on frames of any size (``predict``) with
+instance labelling of the predicted masks (``label_instances``),
 computed by hand-written gfx950 HIP kernels in ``libunet_hip.so`` (C ABI:
 ``include/unet_hip.h``).  The directory name carries hyphens, so import it with
 ``importlib.import_module("image-segmentation-project_amd")``.
@@ -22,6 +23,7 @@ from .synthetic import random_batch, synthetic_cells  # noqa: F401
 from . import dataset  # noqa: F401
 from .dataset import CellAugmenter, CellSegmentationDataset, prepare_data, preprocess  # noqa: F401
 from .predict import predict, tile_origins  # noqa: F401
+from .instances import instance_properties, label_instances  # noqa: F401
 from . import ddp  # noqa: F401
 from . import optim  # noqa: F401
 from .optim import Adam  # noqa: F401

@@ -22,6 +22,7 @@ SOFTMAX_MAX_BLOCKS = 1024
 SOFTMAX_THREADS = 256
 SOFTMAX_SCRATCH_LEN = SOFTMAX_SUMS_LEN * SOFTMAX_MAX_BLOCKS
 TILE_MAX = 1024  # UNET_TILE_MAX: largest tile of unet_tile_gather / unet_tile_blend
+INSTANCE_STATS = 7  # UNET_INSTANCE_STATS: area, sum_y, sum_x, y0, x0, y1, x1
 
 _lib = None
 
@@ -134,6 +135,8 @@ SIGNATURES = {
     "unet_tile_grid": (c_int, [c_int] * 4 + [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "unet_tile_gather": (c_int, [c_void_p] + [c_int] * 5 + [ctypes.c_uint, c_int64, c_int64, c_void_p, c_void_p]),
     "unet_tile_blend": (c_int, [c_void_p] + [c_int] * 6 + [ctypes.c_uint, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "unet_instances_workspace_bytes": (c_int64, [c_int] * 3),
+    "unet_label_instances": (c_int, [c_void_p] + [c_int] * 8 + [c_void_p] * 5 + [c_int64, c_void_p]),
     "unet_maxpool_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
     "unet_maxpool_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 4 + [c_void_p]),
 }

@@ -2626,6 +2626,51 @@ int unet_tile_blend(const float* tile_logits, int N, int K, int H, int W, int T,
 }
 
 // ---------------------------------------------------------------------------
+// Instance labelling of masks (instances.hip)
+// ---------------------------------------------------------------------------
+static bool instances_shape_ok(const char* fn, int N, int H, int W) {
+  if (N > 0 && H > 0 && W > 0 && (int64_t)H * W < kInstMaxHW) return true;
+  char m[200];
+  std::snprintf(m, sizeof(m), "%s: N = %d, H = %d, W = %d must be positive with H * W < 2^31", fn, N, H, W);
+  set_err(m);
+  return false;
+}
+
+int64_t unet_instances_workspace_bytes(int N, int H, int W) {
+  if (!instances_shape_ok("unet_instances_workspace_bytes", N, H, W)) return 0;
+  return instances_workspace_bytes(N, H, W);
+}
+
+int unet_label_instances(const uint8_t* mask, int N, int H, int W, int fg_value, int connectivity, int fill_holes,
+                         int min_area, int max_instances, int32_t* labels, int32_t* counts, int64_t* stats,
+                         uint8_t* filled, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
+  const char* fn = "unet_label_instances";
+  if (!mask || !labels || !counts) { set_err("unet_label_instances: mask / labels / counts is null"); return 1; }
+  if (!instances_shape_ok(fn, N, H, W)) return 1;
+  if (fg_value < -1 || fg_value > 255 || (connectivity != 1 && connectivity != 2) || min_area < 0 ||
+      max_instances < 1) {
+    char m[240];
+    std::snprintf(m, sizeof(m),
+                  "%s: fg_value = %d must be -1 or 0..255, connectivity = %d 1 or 2, min_area = %d >= 0, "
+                  "max_instances = %d >= 1", fn, fg_value, connectivity, min_area, max_instances);
+    set_err(m);
+    return 1;
+  }
+  const int64_t need = instances_workspace_bytes(N, H, W);
+  if (!workspace || workspace_bytes < need) {
+    char m[200];
+    std::snprintf(m, sizeof(m), "%s: workspace null or workspace_bytes %lld < unet_instances_workspace_bytes (%lld)",
+                  fn, (long long)workspace_bytes, (long long)need);
+    set_err(m);
+    return 1;
+  }
+  const InstArgs a{mask, N, H, W, fg_value, connectivity, fill_holes, min_area, max_instances, labels, counts,
+                   reinterpret_cast<long long*>(stats), filled, workspace, workspace_bytes};
+  CK(launch_label_instances(a, stream));
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
 // DDP gradient reduction over RCCL for non-Python hosts (SURVEY.md §8(b):
 // "unet_allreduce_* ... communicator init from a ncclUniqueId byte blob";
 // insertion point /root/reference/train.py:48-49).  RCCL is resolved at run

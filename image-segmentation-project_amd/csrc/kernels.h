@@ -500,6 +500,28 @@ hipError_t launch_tile_gather(const float* image, float* tiles, const TileGeom& 
 hipError_t launch_tile_blend(const float* tile_logits, float* logits, uint8_t* mask, uint8_t* labels,
                              const TileGeom& g, int N, int K, hipStream_t st);
 
+// instance labelling of uint8 masks (instances.hip): connected components with
+// scipy.ndimage.label's numbering, optional hole filling, minimum area, stats.
+constexpr int kInstTH = 32, kInstTW = 64;            // tile of the LDS labelling pass (UNET_INSTANCE_TILE_H / _W)
+constexpr int kInstRankBlock = 2048;                 // elements per block of the ranking prefix sum
+constexpr int64_t kInstMaxHW = (int64_t)1 << 31;     // per-frame indices are int32
+struct InstArgs {
+  const uint8_t* mask;   // [N][H][W]
+  int N, H, W;
+  int fg_value;          // -1: nonzero is foreground; 0..255: == value
+  int conn;              // 1: 4-neighbour, 2: 8-neighbour
+  int fill_holes, min_area, max_inst;
+  int* labels;           // [N][H][W]
+  int* counts;           // [N]
+  long long* stats;      // [N][max_inst][UNET_INSTANCE_STATS] or null
+  uint8_t* filled;       // [N][H][W] or null
+  void* workspace; int64_t workspace_bytes;
+};
+// 0 for N, H, W <= 0 or H W >= 2^31
+int64_t instances_workspace_bytes(int N, int H, int W);
+// hipErrorInvalidValue (nothing launched) on a null buffer, a bad argument or a short workspace
+hipError_t launch_label_instances(const InstArgs& a, hipStream_t st);
+
 // attention decoder (attention.hip; advanced_models.py:7-61)
 struct AttGateArgs {
   const bf16_t* s; int lds;            // relu(BN_g + BN_x), F_int channels

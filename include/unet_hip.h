@@ -15,6 +15,8 @@
  *   unet_mask_metrics    calculate_metrics tp/fp/fn/tn counts (utils.py:120-151)
  *   unet_softmax_loss_forward / _backward   softmax CE / multi-class Dice on integer label maps
  *   unet_confusion_matrix                    argmax confusion matrix of the same inputs
+ *   unet_label_instances connected-component instances of a predicted mask (scipy.ndimage
+ *                        definitions; the reference's host-side post-processing is not ported)
  *   unet_adam_step       optimizer.step() of torch.optim.Adam(model.parameters(),
  *                        lr, weight_decay) (train.py:49,331-335)
  *   unet_conv_* / unet_maxpool_* / unet_bn_*   single ops of the graph above
@@ -461,6 +463,47 @@ int unet_tile_gather(const float* image, int N, int H, int W, int T, int overlap
  * (unet_confusion_matrix' rule; needs K >= 2). */
 int unet_tile_blend(const float* tile_logits, int N, int K, int H, int W, int T, int overlap, unsigned tta,
                     float* logits, uint8_t* mask, uint8_t* labels, hipStream_t stream);
+
+/* ---- instance labelling of masks (no reference counterpart; the definitions
+ * are scipy.ndimage's: label, binary_fill_holes, find_objects) ----
+ * mask uint8 [N][H][W]; a pixel is foreground when it is nonzero (fg_value = -1)
+ * or equals fg_value (0..255).  Frames are independent.  H W < 2^31.
+ * Order of operations: fill holes, then label, then min_area.
+ *   fill_holes: a hole is a 4-connected component of the background that touches
+ *     no frame edge (binary_fill_holes with its default structure); holes become
+ *     foreground.  filled (nullable) receives the filled mask as 0 / 1; it is
+ *     written only when fill_holes is set.
+ *   labels int32 [N][H][W]: 0 for background, otherwise the instance id.  The
+ *     instances of a frame (connectivity 1: 4-neighbour, 2: 8-neighbour) are
+ *     numbered 1..counts[n] in raster order of their first pixel, i.e. by
+ *     ascending minimum flat index y W + x (scipy.ndimage.label's numbering).
+ *   min_area: components with fewer pixels are removed (label 0) before the
+ *     numbering, so the ids stay consecutive.
+ *   counts int32 [N]: the true number of instances of each frame, also above
+ *     max_instances; the label map is always complete.
+ *   stats (nullable) int64 [N][max_instances][UNET_INSTANCE_STATS]: row id - 1 =
+ *     {area, sum_y, sum_x, y0, x0, y1, x1} with the half-open bounding box
+ *     [y0, y1) x [x0, x1) of find_objects; centroid = sums / area.  Only ids <=
+ *     max_instances have a row; rows at and beyond min(counts[n], max_instances)
+ *     are zero.
+ * Integer arithmetic throughout: the outputs are bit-reproducible.  The passes
+ * work on tiles of UNET_INSTANCE_TILE_H x UNET_INSTANCE_TILE_W pixels.
+ * workspace: at least unet_instances_workspace_bytes(N, H, W) bytes of device
+ * memory, 256-B aligned as an allocator returns it; it need not be initialised
+ * and holds nothing between calls.  A short workspace is an error with nothing
+ * launched. */
+#define UNET_INSTANCE_STATS 7
+#define UNET_INSTANCE_TILE_H 32
+#define UNET_INSTANCE_TILE_W 64
+/* host only; 0 (with unet_last_error) for N, H, W <= 0 or H W >= 2^31 */
+int64_t unet_instances_workspace_bytes(int N, int H, int W);
+int unet_label_instances(const uint8_t* mask, int N, int H, int W,
+                         int fg_value /* -1: nonzero; 0..255: == value */,
+                         int connectivity /* 1: 4-neighbour, 2: 8-neighbour */,
+                         int fill_holes, int min_area, int max_instances,
+                         int32_t* labels, int32_t* counts /* [N] */,
+                         int64_t* stats /* nullable */, uint8_t* filled /* nullable */,
+                         void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
 #ifdef __cplusplus
 }
