@@ -23,6 +23,8 @@ SOFTMAX_THREADS = 256
 SOFTMAX_SCRATCH_LEN = SOFTMAX_SUMS_LEN * SOFTMAX_MAX_BLOCKS
 TILE_MAX = 1024  # UNET_TILE_MAX: largest tile of unet_tile_gather / unet_tile_blend
 INSTANCE_STATS = 7  # UNET_INSTANCE_STATS: area, sum_y, sum_x, y0, x0, y1, x1
+DISTANCE_NONE = 2147483647  # UNET_DISTANCE_NONE: dist2 of a frame without a site
+DISTANCE_MAX_DIM = 32768  # UNET_DISTANCE_MAX_DIM: largest H and W of the distance transform
 
 _lib = None
 
@@ -137,6 +139,10 @@ SIGNATURES = {
     "unet_tile_blend": (c_int, [c_void_p] + [c_int] * 6 + [ctypes.c_uint, c_void_p, c_void_p, c_void_p, c_void_p]),
     "unet_instances_workspace_bytes": (c_int64, [c_int] * 3),
     "unet_label_instances": (c_int, [c_void_p] + [c_int] * 8 + [c_void_p] * 5 + [c_int64, c_void_p]),
+    "unet_distance_workspace_bytes": (c_int64, [c_int] * 3),
+    "unet_distance_transform": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p] * 3 + [c_int64, c_void_p]),
+    "unet_grow_instances": (c_int, [c_void_p] + [c_int] * 3 + [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64,
+                                                                c_void_p]),
     "unet_maxpool_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
     "unet_maxpool_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 4 + [c_void_p]),
 }

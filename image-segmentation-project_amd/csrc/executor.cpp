@@ -2671,6 +2671,79 @@ int unet_label_instances(const uint8_t* mask, int N, int H, int W, int fg_value,
 }
 
 // ---------------------------------------------------------------------------
+// Distance / nearest-site transform and growth of instances (distance.hip)
+// ---------------------------------------------------------------------------
+static_assert(kDistMaxDim == UNET_DISTANCE_MAX_DIM, "size limit of the header");
+
+static bool distance_shape_ok(const char* fn, int N, int H, int W) {
+  if (N > 0 && H > 0 && W > 0 && H <= kDistMaxDim && W <= kDistMaxDim && (int64_t)H * W < ((int64_t)1 << 31))
+    return true;
+  char m[200];
+  std::snprintf(m, sizeof(m), "%s: N = %d, H = %d, W = %d must be positive with H, W <= %d and H * W < 2^31", fn, N,
+                H, W, kDistMaxDim);
+  set_err(m);
+  return false;
+}
+
+static bool distance_workspace_ok(const char* fn, int N, int H, int W, const void* workspace, int64_t bytes) {
+  const int64_t need = distance_workspace_bytes(N, H, W);
+  if (workspace && bytes >= need) return true;
+  char m[200];
+  std::snprintf(m, sizeof(m), "%s: workspace null or workspace_bytes %lld < unet_distance_workspace_bytes (%lld)", fn,
+                (long long)bytes, (long long)need);
+  set_err(m);
+  return false;
+}
+
+int64_t unet_distance_workspace_bytes(int N, int H, int W) {
+  if (!distance_shape_ok("unet_distance_workspace_bytes", N, H, W)) return 0;
+  return distance_workspace_bytes(N, H, W);
+}
+
+int unet_distance_transform(const void* src, int src_dtype, int N, int H, int W, int fg_value, int sites,
+                            int32_t* dist2, int32_t* nearest, void* workspace, int64_t workspace_bytes,
+                            hipStream_t stream) {
+  const char* fn = "unet_distance_transform";
+  if (!src) { set_err("unet_distance_transform: src is null"); return 1; }
+  if (!dist2 && !nearest) { set_err("unet_distance_transform: dist2 and nearest are both null"); return 1; }
+  if (!distance_shape_ok(fn, N, H, W)) return 1;
+  if ((src_dtype != 0 && src_dtype != 1) || (sites != 0 && sites != 1) || fg_value < -1 ||
+      (src_dtype == 0 && fg_value > 255)) {
+    char m[240];
+    std::snprintf(m, sizeof(m),
+                  "%s: src_dtype = %d must be 0 (uint8) or 1 (int32), sites = %d 0 or 1, fg_value = %d -1 or >= 0 "
+                  "(<= 255 for uint8)", fn, src_dtype, sites, fg_value);
+    set_err(m);
+    return 1;
+  }
+  if (!distance_workspace_ok(fn, N, H, W, workspace, workspace_bytes)) return 1;
+  const DistArgs a{src, src_dtype, N, H, W, fg_value, sites, dist2, nearest, -1, nullptr, -1, nullptr, workspace,
+                   workspace_bytes};
+  CK(launch_distance(a, stream));
+  return 0;
+}
+
+int unet_grow_instances(const int32_t* labels, int N, int H, int W, int64_t max_dist2, const uint8_t* within,
+                        int within_value, int32_t* out, void* workspace, int64_t workspace_bytes,
+                        hipStream_t stream) {
+  const char* fn = "unet_grow_instances";
+  if (!labels || !out) { set_err("unet_grow_instances: labels / out is null"); return 1; }
+  if (out == labels) { set_err("unet_grow_instances: out must not alias labels"); return 1; }
+  if (!distance_shape_ok(fn, N, H, W)) return 1;
+  if (within_value < -1 || within_value > 255) {
+    char m[160];
+    std::snprintf(m, sizeof(m), "%s: within_value = %d must be -1 or 0..255", fn, within_value);
+    set_err(m);
+    return 1;
+  }
+  if (!distance_workspace_ok(fn, N, H, W, workspace, workspace_bytes)) return 1;
+  const DistArgs a{labels, 1, N, H, W, -1, 1, nullptr, nullptr, max_dist2, within, within_value, out, workspace,
+                   workspace_bytes};
+  CK(launch_distance(a, stream));
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
 // DDP gradient reduction over RCCL for non-Python hosts (SURVEY.md §8(b):
 // "unet_allreduce_* ... communicator init from a ncclUniqueId byte blob";
 // insertion point /root/reference/train.py:48-49).  RCCL is resolved at run

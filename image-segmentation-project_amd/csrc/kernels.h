@@ -522,6 +522,34 @@ int64_t instances_workspace_bytes(int N, int H, int W);
 // hipErrorInvalidValue (nothing launched) on a null buffer, a bad argument or a short workspace
 hipError_t launch_label_instances(const InstArgs& a, hipStream_t st);
 
+// exact Euclidean distance / nearest-site transform and nearest-label growth (distance.hip)
+constexpr int kDistColThreads = 64;   // columns per block of the column pass
+constexpr int kDistColRows = 128;    // rows per thread of the column pass (segments of a column on grid.z)
+constexpr int kDistColBatch = 16;     // rows a column thread loads together
+constexpr int kDistRowThreads = 256;  // threads per block of the row pass (one block per row)
+constexpr int kDistGroup = 16;        // columns per group of the row pass (one minimum per group)
+constexpr size_t kDistRowLds = 65536; // LDS bytes of a row block: the row's offsets, then the group minima that fit
+constexpr int kDistMaxDim = 32768;    // H, W <= this: int16 row offsets, the row's offsets fit 64 KiB of LDS
+struct DistArgs {
+  const void* src;       // [N][H][W] uint8 (src_dtype 0) or int32 (1); the labels when growing
+  int src_dtype;
+  int N, H, W;
+  int fg_value;          // -1: nonzero is foreground; >= 0: == value
+  int sites;             // 1: foreground pixels are sites; 0: the others
+  int* dist2;            // [N][H][W] or null
+  int* nearest;          // [N][H][W] or null
+  // growing (out != null): sites are labels != 0, dist2 / nearest are unused
+  int64_t max_dist2;     // < 0: unlimited
+  const uint8_t* within; // [N][H][W] or null
+  int within_value;      // -1: nonzero; 0..255: == value
+  int* out;              // [N][H][W], must not alias src
+  void* workspace; int64_t workspace_bytes;
+};
+// 0 for N, H, W <= 0, H or W > 32768 or H W >= 2^31
+int64_t distance_workspace_bytes(int N, int H, int W);
+// hipErrorInvalidValue (nothing launched) on a null buffer, a bad argument or a short workspace
+hipError_t launch_distance(const DistArgs& a, hipStream_t st);
+
 // attention decoder (attention.hip; advanced_models.py:7-61)
 struct AttGateArgs {
   const bf16_t* s; int lds;            // relu(BN_g + BN_x), F_int channels

@@ -17,6 +17,8 @@
  *   unet_confusion_matrix                    argmax confusion matrix of the same inputs
  *   unet_label_instances connected-component instances of a predicted mask (scipy.ndimage
  *                        definitions; the reference's host-side post-processing is not ported)
+ *   unet_distance_transform / unet_grow_instances   exact Euclidean distance and nearest-site
+ *                        transform of masks and label maps, nearest-label growth of instances
  *   unet_adam_step       optimizer.step() of torch.optim.Adam(model.parameters(),
  *                        lr, weight_decay) (train.py:49,331-335)
  *   unet_conv_* / unet_maxpool_* / unet_bn_*   single ops of the graph above
@@ -504,6 +506,53 @@ int unet_label_instances(const uint8_t* mask, int N, int H, int W,
                          int32_t* labels, int32_t* counts /* [N] */,
                          int64_t* stats /* nullable */, uint8_t* filled /* nullable */,
                          void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
+/* ---- exact Euclidean distance transform, nearest-site transform and growth of
+ * instances (no reference counterpart) ----
+ * Frames [N][H][W] are independent.  H, W <= 32768 and H W < 2^31, so every
+ * squared distance fits an int32.  A set of pixels of each frame are sites; for
+ * every pixel p = (py, px):
+ *   dist2[p]   = min over the sites s of (py - sy)^2 + (px - sx)^2, exact; 0 at a site.
+ *   nearest[p] = the per-frame flat index sy W + sx of a site at that distance;
+ *                among equidistant sites the smallest flat index; at a site its
+ *                own index.
+ *   A frame without a site gives dist2 = UNET_DISTANCE_NONE and nearest = -1.
+ * dist2 equals rint(scipy.ndimage.distance_transform_edt(~site) ** 2); scipy's
+ * return_indices chooses differently among equidistant sites.
+ * unet_distance_transform: src is uint8 (src_dtype 0) or int32 (1).  A pixel is
+ *   foreground when it is nonzero (fg_value = -1) or equals fg_value (>= 0; <=
+ *   255 for uint8).  sites = 0: the pixels that are not foreground are the sites
+ *   (the distance of every foreground pixel to the background, scipy's edt of
+ *   the foreground); sites = 1: the foreground pixels are the sites.  dist2 and
+ *   nearest are each optional, not both null.
+ * unet_grow_instances: nearest-label growth (skimage.segmentation.expand_labels).
+ *   The sites are the pixels with labels != 0.  out[p] = labels[p] where that is
+ *   nonzero; otherwise labels[nearest[p]] when dist2[p] <= max_dist2 (max_dist2
+ *   < 0: no limit) and, if within is given, p is allowed (within[p] nonzero for
+ *   within_value = -1, within[p] == within_value for 0..255); otherwise 0.
+ *   "Nearest" is Euclidean over the whole frame, not geodesic: a label can grow
+ *   across pixels that are not allowed.  The set of ids is unchanged.  out must
+ *   not alias labels.
+ * Integer arithmetic throughout, no atomics: the outputs are bit-reproducible.
+ * workspace: at least unet_distance_workspace_bytes(N, H, W) bytes of device
+ * memory; it need not be initialised and holds nothing between calls.  Every
+ * bad argument (sizes, src_dtype, sites, fg_value, within_value out of range,
+ * a null buffer, both outputs null, out == labels, a short or null workspace)
+ * is an error with nothing launched. */
+#define UNET_DISTANCE_NONE 2147483647
+#define UNET_DISTANCE_MAX_DIM 32768
+/* host only; 0 (with unet_last_error) for N, H, W <= 0, H or W > 32768 or H W >= 2^31 */
+int64_t unet_distance_workspace_bytes(int N, int H, int W);
+int unet_distance_transform(const void* src, int src_dtype /* 0 uint8, 1 int32 */, int N, int H, int W,
+                            int fg_value /* -1: nonzero is foreground; >= 0: == value */,
+                            int sites /* 0: non-foreground pixels are sites; 1: foreground pixels are sites */,
+                            int32_t* dist2 /* nullable */, int32_t* nearest /* nullable */,
+                            void* workspace, int64_t workspace_bytes, hipStream_t stream);
+int unet_grow_instances(const int32_t* labels, int N, int H, int W,
+                        int64_t max_dist2 /* < 0: unlimited */,
+                        const uint8_t* within /* nullable [N][H][W] */, int within_value /* -1: nonzero; 0..255: == */,
+                        int32_t* out /* must not alias labels */,
+                        void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
 #ifdef __cplusplus
 }
