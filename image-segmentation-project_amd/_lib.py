@@ -55,6 +55,38 @@ class ConvExArgs(ctypes.Structure):
         self.size = ctypes.sizeof(ConvExArgs)
 
 
+class AttGateOpArgs(ctypes.Structure):
+    """unet_att_gate_args (include/unet_hip.h): one pass of the attention gate
+    as a single op.  size is filled in here."""
+    _fields_ = ([(n, c_int) for n in (
+        "size", "pass_", "training", "Fi", "Fl", "lds", "ldx", "ldxatt", "lddxatt", "lddxpsi", "lddS", "ldyraw",
+        "ldyraw2")]
+                + [("eps", c_float), ("momentum", c_float), ("npix", c_int64)]
+                + [(n, c_void_p) for n in (
+                    "s", "psi_w", "psi_b", "p", "psi", "dbnp", "pst", "pbs", "save", "gamma", "beta", "run_mean",
+                    "run_var", "nbt", "x", "xatt", "dxatt", "dxpsi", "dS", "gpsi_w", "ggamma", "gbeta", "gpsi_acc",
+                    "yraw", "yraw2", "mean", "invstd", "mean2", "invstd2", "bsums", "bsums2")])
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.size = ctypes.sizeof(AttGateOpArgs)
+
+
+class ChAttOpArgs(ctypes.Structure):
+    """unet_ch_att_args (include/unet_hip.h): one pass of the channel attention
+    as a single op.  size is filled in here."""
+    _fields_ = ([(n, c_int) for n in (
+        "size", "pass_", "N", "C", "Cr", "ldy", "ldo", "lddo2", "lddo", "ldact", "ldyraw")]
+                + [("HW", c_int64)]
+                + [(n, c_void_p) for n in (
+                    "y", "out", "psum", "pkey", "w1", "w2", "am", "h", "gate", "dout2", "dgate", "dam", "gw1", "gw2",
+                    "gw_acc", "dout", "act", "yraw", "mean", "invstd", "bsums")])
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.size = ctypes.sizeof(ChAttOpArgs)
+
+
 # name -> (restype, argtypes); every exported symbol of include/unet_hip.h
 SIGNATURES = {
     "unet_last_error": (c_char_p, []),
@@ -105,6 +137,8 @@ SIGNATURES = {
                       + [c_int] * 12 + [c_void_p]),
     "unet_conv_ex": (c_int, [ctypes.POINTER(ConvExArgs), c_void_p]),
     "unet_last_kernel_tag": (c_char_p, []),
+    "unet_att_gate_op": (c_int, [ctypes.POINTER(AttGateOpArgs), c_void_p]),
+    "unet_ch_att_op": (c_int, [ctypes.POINTER(ChAttOpArgs), c_void_p]),
     "unet_conv_wgrad": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p] + [c_int] * 12 + [c_void_p]),
     "unet_conv3x3_fl": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                 c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,

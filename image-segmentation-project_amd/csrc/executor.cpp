@@ -2402,6 +2402,163 @@ int unet_conv_ex(const unet_conv_ex_args* p, hipStream_t stream) {
   return err == hipSuccess ? 0 : refused(err);
 }
 
+// ---- attention single ops: argument checks, then the launcher's pass as it is ----
+namespace {
+// the checks shared by unet_att_gate_op / unet_ch_att_op; the first failure is kept
+struct OpCheck {
+  const char* fn;
+  bool ok = true;
+  int fail(const std::string& m) {
+    if (ok) set_err(std::string(fn) + ": " + m);
+    ok = false;
+    return 1;
+  }
+  void ptr(const void* q, const char* name, int pass) {
+    if (ok && !q) fail(std::string(name) + " is null (pass " + std::to_string(pass) + " uses it)");
+  }
+  // a bf16 NHWC tensor read / written as 16-B chunks of 8 channels
+  void act(const void* q, int ld, int width, const char* name, const char* ldname, int pass) {
+    ptr(q, name, pass);
+    if (ok && ((uintptr_t)q & 15)) fail(std::string(name) + " must be 16-byte aligned");
+    if (ok && ld < width) fail(std::string(ldname) + " is smaller than the width " + std::to_string(width));
+    if (ok && ld % 8) fail(std::string(ldname) + " must be a multiple of 8");
+  }
+};
+}  // namespace
+
+int unet_att_gate_op(const unet_att_gate_args* p, hipStream_t stream) {
+  OpCheck k{"unet_att_gate_op"};
+  if (!p || p->size != (int)sizeof(unet_att_gate_args)) return k.fail("null argument or size != sizeof(unet_att_gate_args)");
+  const unet_att_gate_args& e = *p;
+  const int ps = e.pass;
+  if (ps < 0 || ps > 3) return k.fail("pass must be 0..3");
+  if (e.training != 0 && e.training != 1) return k.fail("training must be 0 or 1");
+  if (e.npix <= 0) return k.fail("npix must be positive");
+  auto width_ok = [](int F) { return F >= 8 && F % 8 == 0 && 64 % (F / 8) == 0; };
+  if (!width_ok(e.Fi)) return k.fail("Fi / 8 must divide 64 (Fi = 8, 16, 32, 64, 128, 256 or 512)");
+  if (!width_ok(e.Fl)) return k.fail("Fl / 8 must divide 64 (Fl = 8, 16, 32, 64, 128, 256 or 512)");
+  const bool bbany = e.yraw || e.yraw2 || e.mean || e.invstd || e.mean2 || e.invstd2 || e.bsums || e.bsums2 ||
+                     e.ldyraw || e.ldyraw2;
+  if (ps == 0) {
+    k.act(e.s, e.lds, e.Fi, "s", "lds", ps);
+    k.ptr(e.psi_w, "psi_w", ps); k.ptr(e.psi_b, "psi_b", ps); k.ptr(e.p, "p", ps);
+    if (e.training) k.ptr(e.pst, "pst", ps);
+  } else if (ps == 1) {
+    k.ptr(e.p, "p", ps); k.ptr(e.psi, "psi", ps); k.ptr(e.gamma, "gamma", ps); k.ptr(e.beta, "beta", ps);
+    k.ptr(e.run_mean, "run_mean", ps); k.ptr(e.run_var, "run_var", ps);
+    if (e.training) { k.ptr(e.pst, "pst", ps); k.ptr(e.save, "save", ps); }
+    k.act(e.x, e.ldx, e.Fl, "x", "ldx", ps);
+    k.act(e.xatt, e.ldxatt, e.Fl, "xatt", "ldxatt", ps);
+    if (k.ok && !(e.eps > 0.f)) k.fail("eps must be > 0");
+  } else if (ps == 2) {
+    k.ptr(e.save, "save", ps); k.ptr(e.psi, "psi", ps); k.ptr(e.p, "p", ps); k.ptr(e.dbnp, "dbnp", ps);
+    k.ptr(e.pbs, "pbs", ps);
+    k.act(e.x, e.ldx, e.Fl, "x", "ldx", ps);
+    k.act(e.dxatt, e.lddxatt, e.Fl, "dxatt", "lddxatt", ps);
+    k.act(e.dxpsi, e.lddxpsi, e.Fl, "dxpsi", "lddxpsi", ps);
+  } else {
+    k.ptr(e.save, "save", ps); k.ptr(e.pbs, "pbs", ps); k.ptr(e.gamma, "gamma", ps); k.ptr(e.psi_w, "psi_w", ps);
+    k.ptr(e.p, "p", ps); k.ptr(e.dbnp, "dbnp", ps); k.ptr(e.gpsi_acc, "gpsi_acc", ps); k.ptr(e.gpsi_w, "gpsi_w", ps);
+    k.ptr(e.ggamma, "ggamma", ps); k.ptr(e.gbeta, "gbeta", ps);
+    k.act(e.s, e.lds, e.Fi, "s", "lds", ps);
+    k.act(e.dS, e.lddS, e.Fi, "dS", "lddS", ps);
+    if (k.ok && bbany) {
+      if (!e.bsums || !e.bsums2 || !e.mean || !e.invstd || !e.mean2 || !e.invstd2 || !e.yraw || !e.yraw2)
+        return k.fail("the fused BN backward (bb) needs all of yraw, yraw2, mean, invstd, mean2, invstd2, bsums, bsums2");
+      k.act(e.yraw, e.ldyraw, e.Fi, "yraw", "ldyraw", ps);
+      k.act(e.yraw2, e.ldyraw2, e.Fi, "yraw2", "ldyraw2", ps);
+    }
+  }
+  if (!k.ok) return 1;
+
+  AttGateArgs a = {};
+  a.s = (const bf16_t*)e.s; a.lds = e.lds; a.psi_w = e.psi_w; a.psi_b = e.psi_b;
+  a.p = e.p; a.psi = e.psi; a.dbnp = e.dbnp; a.pst = e.pst; a.pbs = e.pbs; a.save = e.save;
+  a.gamma = e.gamma; a.beta = e.beta; a.run_mean = e.run_mean; a.run_var = e.run_var; a.nbt = e.nbt;
+  a.count = (double)e.npix; a.eps = e.eps; a.momentum = e.momentum; a.training = e.training;
+  a.x = (const bf16_t*)e.x; a.ldx = e.ldx; a.xatt = (bf16_t*)e.xatt; a.ldxatt = e.ldxatt;
+  a.dxatt = (const bf16_t*)e.dxatt; a.lddxatt = e.lddxatt; a.dxpsi = (bf16_t*)e.dxpsi; a.lddxpsi = e.lddxpsi;
+  a.dS = (bf16_t*)e.dS; a.lddS = e.lddS;
+  a.gpsi_w = e.gpsi_w; a.ggamma = e.ggamma; a.gbeta = e.gbeta; a.gpsi_acc = e.gpsi_acc;
+  if (ps == 3 && bbany) {
+    a.bb.y = (const bf16_t*)e.yraw; a.bb.ldy = e.ldyraw; a.bb.y2 = (const bf16_t*)e.yraw2; a.bb.ldy2 = e.ldyraw2;
+    a.bb.mean = e.mean; a.bb.invstd = e.invstd; a.bb.mean2 = e.mean2; a.bb.invstd2 = e.invstd2;
+    a.bb.sums = e.bsums; a.bb.sums2 = e.bsums2;
+    a.bb.act = a.s; a.bb.ldact = a.lds; a.bb.npix = e.npix; a.bb.C = e.Fi; a.bb.relu = 1;
+  }
+  a.npix = e.npix; a.Fi = e.Fi; a.Fl = e.Fl;
+  const hipError_t err = launch_att_gate(a, ps, stream);
+  if (err != hipSuccess) {
+    set_err(std::string("unet_att_gate_op: launch_att_gate pass ") + std::to_string(ps) + " -> " + hipGetErrorString(err));
+    return (int)err;
+  }
+  return 0;
+}
+
+int unet_ch_att_op(const unet_ch_att_args* p, hipStream_t stream) {
+  OpCheck k{"unet_ch_att_op"};
+  if (!p || p->size != (int)sizeof(unet_ch_att_args)) return k.fail("null argument or size != sizeof(unet_ch_att_args)");
+  const unet_ch_att_args& e = *p;
+  const int ps = e.pass;
+  if (ps < 0 || ps > 5) return k.fail("pass must be 0..5");
+  if (e.C < 8 || e.C % 8 || e.C / 8 > 256 || 256 % (e.C / 8))
+    return k.fail("C / 8 must divide 256 (C = 8, 16, 32, 64, 128, 256, 512, 1024 or 2048)");
+  if (e.Cr <= 0) return k.fail("Cr must be positive");
+  if (e.N <= 0 || e.N > 65535) return k.fail("N must be 1..65535");
+  if (e.HW <= 0 || e.HW > 0xFFFFFFFEll) return k.fail("HW must be 1..2^32-2 (the argmax key holds a 32-bit pixel index)");
+  const bool bbany = e.act || e.yraw || e.mean || e.invstd || e.bsums || e.ldact || e.ldyraw;
+  if (ps == 0) {
+    k.act(e.y, e.ldy, e.C, "y", "ldy", ps);
+    k.ptr(e.psum, "psum", ps); k.ptr(e.pkey, "pkey", ps);
+  } else if (ps == 1) {
+    k.ptr(e.psum, "psum", ps); k.ptr(e.pkey, "pkey", ps); k.ptr(e.w1, "w1", ps); k.ptr(e.w2, "w2", ps);
+    k.ptr(e.am, "am", ps); k.ptr(e.h, "h", ps); k.ptr(e.gate, "gate", ps);
+  } else if (ps == 2) {
+    k.act(e.y, e.ldy, e.C, "y", "ldy", ps);
+    k.ptr(e.gate, "gate", ps);
+    k.act(e.out, e.ldo, e.C, "out", "ldo", ps);
+  } else if (ps == 3) {
+    k.act(e.dout2, e.lddo2, e.C, "dout2", "lddo2", ps);
+    k.act(e.y, e.ldy, e.C, "y", "ldy", ps);
+    k.ptr(e.dgate, "dgate", ps);
+  } else if (ps == 4) {
+    k.ptr(e.gate, "gate", ps); k.ptr(e.dgate, "dgate", ps); k.ptr(e.w1, "w1", ps); k.ptr(e.w2, "w2", ps);
+    k.ptr(e.h, "h", ps); k.ptr(e.am, "am", ps); k.ptr(e.dam, "dam", ps); k.ptr(e.gw_acc, "gw_acc", ps);
+    k.ptr(e.gw1, "gw1", ps); k.ptr(e.gw2, "gw2", ps);
+  } else {
+    k.ptr(e.gate, "gate", ps); k.ptr(e.dam, "dam", ps); k.ptr(e.pkey, "pkey", ps);
+    k.act(e.dout2, e.lddo2, e.C, "dout2", "lddo2", ps);
+    k.act(e.dout, e.lddo, e.C, "dout", "lddo", ps);
+    if (k.ok && bbany) {
+      if (!e.bsums || !e.act || !e.yraw || !e.mean || !e.invstd)
+        return k.fail("the fused BN backward (bb) needs all of act, yraw, mean, invstd, bsums");
+      k.act(e.act, e.ldact, e.C, "act", "ldact", ps);
+      k.act(e.yraw, e.ldyraw, e.C, "yraw", "ldyraw", ps);
+    }
+  }
+  if (!k.ok) return 1;
+
+  ChAttArgs c = {};
+  c.y = (const bf16_t*)e.y; c.ldy = e.ldy; c.out = (bf16_t*)e.out; c.ldo = e.ldo;
+  c.psum = e.psum; c.pkey = e.pkey; c.w1 = e.w1; c.w2 = e.w2; c.am = e.am; c.h = e.h; c.gate = e.gate;
+  c.dout2 = (const bf16_t*)e.dout2; c.lddo2 = e.lddo2; c.dgate = e.dgate; c.dam = e.dam;
+  c.gw1 = e.gw1; c.gw2 = e.gw2; c.gw_acc = e.gw_acc;
+  c.dout = (bf16_t*)e.dout; c.lddo = e.lddo;
+  if (ps == 5 && bbany) {
+    c.bb.act = (const bf16_t*)e.act; c.bb.ldact = e.ldact; c.bb.y = (const bf16_t*)e.yraw; c.bb.ldy = e.ldyraw;
+    c.bb.mean = e.mean; c.bb.invstd = e.invstd; c.bb.sums = e.bsums;
+    c.bb.npix = (int64_t)e.N * e.HW; c.bb.C = e.C; c.bb.relu = 1;
+  }
+  c.HW = e.HW; c.inv_hw = 1.0f / (float)e.HW;  // as the executor's ch_args
+  c.N = e.N; c.C = e.C; c.Cr = e.Cr;
+  const hipError_t err = launch_ch_att(c, ps, stream);
+  if (err != hipSuccess) {
+    set_err(std::string("unet_ch_att_op: launch_ch_att pass ") + std::to_string(ps) + " -> " + hipGetErrorString(err));
+    return (int)err;
+  }
+  return 0;
+}
+
 int unet_f8_quantize(const void* x, int ld, int C, int64_t npix, void* q, void* state, int calibrate,
                      hipStream_t stream) {
   CK(launch_f8_quant_act((const bf16_t*)x, ld, C, npix, (uint8_t*)q, (F8State*)state, calibrate, stream));

@@ -351,6 +351,90 @@ int unet_conv_ex(const unet_conv_ex_args* args, hipStream_t stream);
  * ("conv3x3_hs_kernel<2, 16, 8, true, false, false>", ...): tests assert which
  * instance the dispatch selected */
 const char* unet_last_kernel_tag(void);
+/* ---- attention decoder as single ops (advanced_models.py:7-61), for tests ----
+ * One call runs ONE pass of the AttentionGate (psi conv1x1 + BN(1) + sigmoid +
+ * x * psi, advanced_models.py:28-40) or of the ChannelAttention (avg / first-
+ * argmax max pooling, the shared C -> Cr -> C MLP, sigmoid, channel scale,
+ * advanced_models.py:56-61): the launch the executor makes for that pass, with
+ * the launchers' own pass numbers.  size = sizeof(the struct) (checked).  The
+ * caller owns every buffer, the accumulators included, and zeroes them; nothing
+ * is allocated, zeroed or finalised here.  Everything is checked before any
+ * launch (unet_last_error names the field): a null buffer that the chosen pass
+ * reads or writes, a misaligned (16 B) bf16 buffer, a leading dimension that is
+ * not a multiple of 8 or is smaller than the width, a refused width, a fused
+ * BN backward that is only partly given.  Buffers and leading dimensions that
+ * the chosen pass does not use are not examined, so one filled struct serves
+ * all passes; the fused fields are examined in the pass that fuses (gate 3,
+ * channel attention 5) and must be null / 0 to switch the fusion off.
+ * bf16 tensors are NHWC with the given channel stride; pixel counts: npix = N H W,
+ * HW per image.
+ *
+ * unet_att_gate_op; Fi, Fl in {8, 16, 32, 64, 128, 256, 512} (F / 8 lanes share
+ * a pixel and must tile a wave), npix > 0, BN(1) count = npix.  Per pass:
+ *   0  p = psi_b + s . psi_w.  Reads s (lds, Fi), psi_w [Fi], psi_b [1]; writes
+ *      p [npix]; training: adds sum p, sum p^2 into pst [2] (fp64, ZEROED).
+ *   1  psi = sigmoid(BN(p)), xatt = x * psi.  Reads p, x (ldx, Fl), gamma, beta
+ *      [1], eps > 0; training: pst (of pass 0), writes save [2] = mean, invstd,
+ *      updates run_mean / run_var [1] (momentum, unbiased variance) and nbt += 1
+ *      (int64; null: untouched); eval: reads run_mean / run_var, touches neither
+ *      pst, save, the running statistics nor nbt.  Writes psi [npix], xatt (ldxatt).
+ *   2  Reads save, psi, p, x, dxatt (lddxatt); writes dxpsi = dxatt * psi
+ *      (lddxpsi), dbnp [npix] = dZ of the BN, adds sum dZ, sum dZ phat into pbs
+ *      [2] (fp64, ZEROED).
+ *   3  Reads save, pbs (of pass 2), gamma, psi_w, p, dbnp, s; writes dS (lddS,
+ *      Fi) = dp * psi_w, ggamma, gbeta [1]; adds the psi weight gradient into
+ *      gpsi_acc (fp64 [16][Fi], ZEROED) and writes its replica sum to gpsi_w
+ *      [Fi].  Fused (bsums != null; all of yraw, yraw2 (ldyraw, ldyraw2 >= Fi),
+ *      mean, invstd, mean2, invstd2 [Fi], bsums, bsums2): dS is stored as dZ =
+ *      dS * (s > 0) and sum dZ, sum dZ xhat go to rows 0, 1 of bsums, sum dZ
+ *      xhat2 to row 1 of bsums2 (fp64 [16][2][Fi] replicas, ZEROED; row 0 of
+ *      bsums2 is not written: both BNs share sum dZ).
+ *
+ * unet_ch_att_op; C in {8, 16, 32, 64, 128, 256, 512, 1024, 2048} (C / 8 must
+ * divide 256), Cr > 0, N > 0, 0 < HW <= 2^32 - 2.  Per pass:
+ *   0  Reads y (ldy); adds the per-(n, c) sums into psum (fp64 [N][C], ZEROED)
+ *      and merges pkey (u64 [N][C], ZEROED) = (order-preserving key of the
+ *      maximum) << 32 | (2^32 - 1 - first pixel index of the maximum).
+ *   1  Reads psum, pkey, w1 [Cr][C], w2 [C][Cr]; writes am [N][2][C] = avg | max,
+ *      h [N][2][Cr], gate [N][C].
+ *   2  Reads y, gate; writes out = y * gate (ldo).
+ *   3  Reads dout2 (lddo2), y; adds sum_hw dout2 * y into dgate (fp64 [N][C], ZEROED).
+ *   4  Reads gate, dgate, w1, w2, h, am; writes dam [N][2][C]; adds the weight
+ *      gradients into gw_acc (fp64 [16][2][C Cr]: fc.2 | fc.0, ZEROED) and writes
+ *      their replica sums to gw2 [C][Cr], gw1 [Cr][C].
+ *   5  Reads gate, dam, pkey, dout2; writes dout (lddo) = dout2 * gate + davg / HW
+ *      + [hw == argmax] dmax.  Fused (bsums != null; all of act, yraw (ldact,
+ *      ldyraw >= C), mean, invstd [C], bsums): dout is stored as dZ = dout *
+ *      (act > 0) and sum dZ, sum dZ xhat go to bsums (fp64 [16][2][C], ZEROED). */
+typedef struct unet_att_gate_args {
+  int size, pass, training, Fi, Fl;
+  int lds, ldx, ldxatt, lddxatt, lddxpsi, lddS, ldyraw, ldyraw2;
+  float eps, momentum;
+  int64_t npix;
+  const void* s; const float* psi_w; const float* psi_b;
+  float* p; float* psi; float* dbnp;
+  double* pst; double* pbs; float* save;
+  const float* gamma; const float* beta; float* run_mean; float* run_var; long long* nbt;
+  const void* x; void* xatt; const void* dxatt; void* dxpsi; void* dS;
+  float* gpsi_w; float* ggamma; float* gbeta; double* gpsi_acc;
+  const void* yraw; const void* yraw2; const float* mean; const float* invstd;
+  const float* mean2; const float* invstd2; double* bsums; double* bsums2;
+} unet_att_gate_args;
+int unet_att_gate_op(const unet_att_gate_args* args, hipStream_t stream);
+typedef struct unet_ch_att_args {
+  int size, pass, N, C, Cr;
+  int ldy, ldo, lddo2, lddo, ldact, ldyraw;
+  int64_t HW;
+  const void* y; void* out;
+  double* psum; unsigned long long* pkey;
+  const float* w1; const float* w2;
+  float* am; float* h; float* gate;
+  const void* dout2; double* dgate; float* dam;
+  float* gw1; float* gw2; double* gw_acc;
+  void* dout;
+  const void* act; const void* yraw; const float* mean; const float* invstd; double* bsums;
+} unet_ch_att_args;
+int unet_ch_att_op(const unet_ch_att_args* args, hipStream_t stream);
 /* ---- fp8 e4m3 forward conv (BASELINE.json configs[4]; no reference counterpart:
  * the reference's convs are fp32 torch.nn.Conv2d, advanced_models.py:72-100) ----
  * state: 16-B scale state {amax prev (float bits), amax this step, e8m0 code,
