@@ -7,7 +7,8 @@ plus softmax losses and argmax metrics for mutually exclusive classes
 (``CrossEntropyLoss``, ``SoftmaxDiceLoss``, ``SoftmaxComboLoss``, ``confusion_matrix``)
 and tiled whole-frame inference on frames of any size (``predict``) with
 instance labelling of the predicted masks (``label_instances``), exact distance
-maps and growth of the instances (``distance_transform``, ``grow_instances``),
+maps and growth of the instances (``distance_transform``, ``grow_instances``) and
+their scores against a ground truth (``match_instances``, ``instance_metrics``),
 computed by hand-written gfx950 HIP kernels in ``libunet_hip.so`` (C ABI:
 ``include/unet_hip.h``).  The directory name carries hyphens, so import it with
 ``importlib.import_module("image-segmentation-project_amd")``.
@@ -26,6 +27,7 @@ from .dataset import CellAugmenter, CellSegmentationDataset, prepare_data, prepr
 from .predict import predict, tile_origins  # noqa: F401
 from .instances import instance_properties, label_instances  # noqa: F401
 from .distance import distance_transform, grow_instances  # noqa: F401
+from .match import InstanceMatch, instance_metrics, match_instances  # noqa: F401
 from . import ddp  # noqa: F401
 from . import optim  # noqa: F401
 from .optim import Adam  # noqa: F401

@@ -25,6 +25,8 @@ TILE_MAX = 1024  # UNET_TILE_MAX: largest tile of unet_tile_gather / unet_tile_b
 INSTANCE_STATS = 7  # UNET_INSTANCE_STATS: area, sum_y, sum_x, y0, x0, y1, x1
 DISTANCE_NONE = 2147483647  # UNET_DISTANCE_NONE: dist2 of a frame without a site
 DISTANCE_MAX_DIM = 32768  # UNET_DISTANCE_MAX_DIM: largest H and W of the distance transform
+MATCH_COLS = 4  # UNET_MATCH_COLS: area, partner, intersection, partner_area
+MATCH_STATUS = 5  # UNET_MATCH_STATUS: n_gt, n_pred, n_pairs, dropped, out_of_range
 
 _lib = None
 
@@ -177,7 +179,9 @@ SIGNATURES = {
     "unet_distance_transform": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p] * 3 + [c_int64, c_void_p]),
     "unet_grow_instances": (c_int, [c_void_p] + [c_int] * 3 + [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64,
                                                                 c_void_p]),
-    "unet_maxpool_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
+    "unet_match_workspace_bytes": (c_int64, [c_int] * 4),
+    "unet_match_instances": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p] * 5 + [c_int64, c_void_p]),
+    "unet_maxpool_fwd": (c_int,[c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
     "unet_maxpool_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 4 + [c_void_p]),
 }
 

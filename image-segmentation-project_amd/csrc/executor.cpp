@@ -2901,6 +2901,50 @@ int unet_grow_instances(const int32_t* labels, int N, int H, int W, int64_t max_
 }
 
 // ---------------------------------------------------------------------------
+// Matching of two instance label maps (match.hip)
+// ---------------------------------------------------------------------------
+static bool match_caps_ok(const char* fn, int N, int max_gt, int max_pred, int max_pairs) {
+  if (N > 0 && max_gt >= 1 && max_gt <= kMatchMaxId && max_pred >= 1 && max_pred <= kMatchMaxId && max_pairs >= 1 &&
+      max_pairs <= kMatchMaxPairs)
+    return true;
+  char m[240];
+  std::snprintf(m, sizeof(m), "%s: N = %d must be positive, max_gt = %d and max_pred = %d in 1..%d, max_pairs = %d "
+                "in 1..%d", fn, N, max_gt, max_pred, kMatchMaxId, max_pairs, kMatchMaxPairs);
+  set_err(m);
+  return false;
+}
+
+int64_t unet_match_workspace_bytes(int N, int max_gt, int max_pred, int max_pairs) {
+  if (!match_caps_ok("unet_match_workspace_bytes", N, max_gt, max_pred, max_pairs)) return 0;
+  return match_workspace_bytes(N, max_gt, max_pred, max_pairs);
+}
+
+int unet_match_instances(const int32_t* gt, const int32_t* pred, int N, int H, int W, int max_gt, int max_pred,
+                         int max_pairs, int64_t* gt_table, int64_t* pred_table, int64_t* status, int64_t* pairs,
+                         void* workspace, int64_t workspace_bytes, hipStream_t stream) {
+  const char* fn = "unet_match_instances";
+  if (!gt || !pred || !gt_table || !pred_table || !status) {
+    set_err("unet_match_instances: gt / pred / gt_table / pred_table / status is null");
+    return 1;
+  }
+  if (!instances_shape_ok(fn, N, H, W)) return 1;
+  if (!match_caps_ok(fn, N, max_gt, max_pred, max_pairs)) return 1;
+  const int64_t need = match_workspace_bytes(N, max_gt, max_pred, max_pairs);
+  if (!workspace || workspace_bytes < need) {
+    char m[200];
+    std::snprintf(m, sizeof(m), "%s: workspace null or workspace_bytes %lld < unet_match_workspace_bytes (%lld)", fn,
+                  (long long)workspace_bytes, (long long)need);
+    set_err(m);
+    return 1;
+  }
+  const MatchArgs a{gt, pred, N, H, W, max_gt, max_pred, max_pairs, reinterpret_cast<long long*>(gt_table),
+                    reinterpret_cast<long long*>(pred_table), reinterpret_cast<long long*>(status),
+                    reinterpret_cast<long long*>(pairs), workspace, workspace_bytes};
+  CK(launch_match_instances(a, stream));
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
 // DDP gradient reduction over RCCL for non-Python hosts (SURVEY.md §8(b):
 // "unet_allreduce_* ... communicator init from a ncclUniqueId byte blob";
 // insertion point /root/reference/train.py:48-49).  RCCL is resolved at run

@@ -550,6 +550,27 @@ int64_t distance_workspace_bytes(int N, int H, int W);
 // hipErrorInvalidValue (nothing launched) on a null buffer, a bad argument or a short workspace
 hipError_t launch_distance(const DistArgs& a, hipStream_t st);
 
+// matching of two instance label maps (match.hip): pair histogram, areas, the
+// partner of highest IoU of every instance on both sides, the list of pairs
+constexpr int kMatchLdsSlots = 512;        // keys of the LDS table of a 32 x 64 tile
+constexpr int kMatchMaxId = 65535;         // ids are 16-bit halves of a 32-bit key
+constexpr int kMatchMaxPairs = 1 << 24;    // global table: the power of two >= 2 max_pairs slots
+struct MatchArgs {
+  const int* gt;          // [N][H][W]
+  const int* pred;        // [N][H][W]
+  int N, H, W;
+  int max_gt, max_pred, max_pairs;
+  long long* gt_table;    // [N][max_gt][UNET_MATCH_COLS]
+  long long* pred_table;  // [N][max_pred][UNET_MATCH_COLS]
+  long long* status;      // [N][UNET_MATCH_STATUS]
+  long long* pairs;       // [N][max_pairs][3] or null
+  void* workspace; int64_t workspace_bytes;
+};
+// 0 for N <= 0, a cap outside 1..65535 or max_pairs outside 1..2^24
+int64_t match_workspace_bytes(int N, int max_gt, int max_pred, int max_pairs);
+// hipErrorInvalidValue (nothing launched) on a null buffer, a bad argument or a short workspace
+hipError_t launch_match_instances(const MatchArgs& a, hipStream_t st);
+
 // attention decoder (attention.hip; advanced_models.py:7-61)
 struct AttGateArgs {
   const bf16_t* s; int lds;            // relu(BN_g + BN_x), F_int channels

@@ -19,6 +19,7 @@
  *                        definitions; the reference's host-side post-processing is not ported)
  *   unet_distance_transform / unet_grow_instances   exact Euclidean distance and nearest-site
  *                        transform of masks and label maps, nearest-label growth of instances
+ *   unet_match_instances IoU tables of predicted instances against a ground truth label map
  *   unet_adam_step       optimizer.step() of torch.optim.Adam(model.parameters(),
  *                        lr, weight_decay) (train.py:49,331-335)
  *   unet_conv_* / unet_maxpool_* / unet_bn_*   single ops of the graph above
@@ -637,6 +638,51 @@ int unet_grow_instances(const int32_t* labels, int N, int H, int W,
                         const uint8_t* within /* nullable [N][H][W] */, int within_value /* -1: nonzero; 0..255: == */,
                         int32_t* out /* must not alias labels */,
                         void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
+/* ---- matching of predicted instances to a ground truth (no reference
+ * counterpart) ----
+ * gt and pred are int32 label maps [N][H][W] of independent frames, H W < 2^31:
+ * 0 is background, the instances carry ids 1..max_gt and 1..max_pred (both caps
+ * in 1..65535; the ids need not be compact).  The pair histogram c(g, p) = the
+ * number of pixels with gt == g and pred == p gives, per frame,
+ *   gt_table int64 [N][max_gt][UNET_MATCH_COLS], row id - 1: area, partner,
+ *     intersection, partner_area.  partner is the instance of pred that overlaps
+ *     the id with the highest IoU = c / (area + partner_area - c), compared
+ *     exactly in integers; among equal IoUs the smaller id.  An id that is absent
+ *     (area 0) or overlaps nothing has partner, intersection and partner_area 0.
+ *   pred_table int64 [N][max_pred][UNET_MATCH_COLS]: the same for the ids of
+ *     pred, with partners among the ids of gt.
+ *   status int64 [N][UNET_MATCH_STATUS]: n_gt and n_pred (the ids with area >
+ *     0), n_pairs (the pairs (g, p), both nonzero, with c > 0), dropped (the
+ *     pixels whose pair found no room in the pair table) and out_of_range (the
+ *     pixels with an id below 0 or above its cap; they take no part).  The
+ *     tables describe the maps exactly when dropped and out_of_range are 0.
+ *   pairs (nullable) int64 [N][max_pairs][3]: gt, pred, intersection of the
+ *     first n_pairs pairs, in no particular order (the set is deterministic when
+ *     n_pairs <= max_pairs; beyond that an unspecified max_pairs of them); the
+ *     remaining rows are 0.
+ * The pair table of a frame has the smallest power of two >= 2 max_pairs slots
+ * and holds the pairs with one id 0 (instance against background) as well;
+ * max_pairs outside 1..2^24 is an error.
+ * Integer arithmetic and integer atomics throughout: the outputs are
+ * bit-reproducible.  gt and pred are only read.
+ * workspace: at least unet_match_workspace_bytes(...) bytes of device memory; it
+ * need not be initialised and holds nothing between calls.  It begins with the
+ * pair table of the call: uint32 keys [N][slots] (g << 16 | p, 0 = empty), then
+ * int32 counts [N][slots].  Every bad argument (a null buffer other than pairs,
+ * N, H or W <= 0, H W >= 2^31, a cap or max_pairs out of range, a short or null
+ * workspace) is an error with nothing launched. */
+#define UNET_MATCH_COLS 4     /* area, partner, intersection, partner_area */
+#define UNET_MATCH_STATUS 5   /* n_gt, n_pred, n_pairs, dropped, out_of_range */
+/* host only; 0 (with unet_last_error) for a bad argument */
+int64_t unet_match_workspace_bytes(int N, int max_gt, int max_pred, int max_pairs);
+int unet_match_instances(const int32_t* gt, const int32_t* pred, int N, int H, int W,
+                         int max_gt, int max_pred, int max_pairs,
+                         int64_t* gt_table,    /* [N][max_gt][4]   row id - 1 */
+                         int64_t* pred_table,  /* [N][max_pred][4] */
+                         int64_t* status,      /* [N][5] */
+                         int64_t* pairs,       /* nullable [N][max_pairs][3]: gt, pred, intersection */
+                         void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
 #ifdef __cplusplus
 }
