@@ -13,51 +13,12 @@ from __future__ import annotations
 
 import math
 
-import numpy as np
 import torch
 
 from . import _lib
+from ._frames import as_frames, frames_on_gpu, workspace
 
 _MASK_DTYPES = (torch.uint8, torch.bool, torch.int32)
-
-
-def _as_frames(x, what, dtypes):
-    """Validate an array or tensor of frames; raises ValueError, touches no GPU."""
-    names = " / ".join(str(d).replace("torch.", "") for d in dtypes)
-    if isinstance(x, np.ndarray):
-        if x.dtype not in (np.uint8, np.bool_, np.int32):
-            raise ValueError(f"{what} must be {names}, got {x.dtype}")
-        x = torch.from_numpy(np.ascontiguousarray(x))
-    if not isinstance(x, torch.Tensor):
-        raise ValueError(f"{what} must be a tensor or an array, got {type(x).__name__}")
-    if x.dtype not in dtypes:
-        raise ValueError(f"{what} must be {names}, got {x.dtype}")
-    if x.dim() not in (2, 3, 4):
-        raise ValueError(f"{what} must be [H, W], [N, H, W] or [N, K, H, W], got {tuple(x.shape)}")
-    if x.numel() == 0:
-        raise ValueError(f"{what} is empty")
-    H, W = x.shape[-2:]
-    if H > _lib.DISTANCE_MAX_DIM or W > _lib.DISTANCE_MAX_DIM or H * W >= 1 << 31:
-        raise ValueError(f"{what}: H = {H}, W = {W} must be <= {_lib.DISTANCE_MAX_DIM} with H * W below 2^31")
-    return x
-
-
-def _frames_on_gpu(x):
-    """[M, H, W] contiguous uint8 / int32 device view or copy of a validated tensor"""
-    if not x.is_cuda:
-        _lib.require_gpu()
-        x = x.cuda()
-    _lib.require_gpu(x)
-    if x.dtype == torch.bool:
-        x = x.view(torch.uint8)
-    return x.reshape(-1, x.shape[-2], x.shape[-1]).contiguous()
-
-
-def _workspace(lib, N, H, W, dev):
-    nbytes = int(lib.unet_distance_workspace_bytes(N, H, W))
-    if nbytes <= 0:
-        _lib.check(1, "unet_distance_workspace_bytes")
-    return torch.empty((nbytes,), dtype=torch.uint8, device=dev), nbytes
 
 
 def distance_transform(mask, foreground=None, invert=False, squared=False, return_nearest=False):
@@ -78,20 +39,20 @@ def distance_transform(mask, foreground=None, invert=False, squared=False, retur
     smallest index among equidistant ones, -1 where there is none).  The input
     is not modified and nothing synchronises with the host.
     """
-    mask = _as_frames(mask, "distance_transform: mask", _MASK_DTYPES)
+    mask = as_frames(mask, "distance_transform: mask", _MASK_DTYPES, _lib.DISTANCE_MAX_DIM)
     top = 255 if mask.dtype != torch.int32 else (1 << 31) - 1
     if foreground is not None and not 0 <= int(foreground) <= top:
         raise ValueError(f"foreground={foreground} is outside 0..{top}")
     fgv = -1 if foreground is None else int(foreground)
     shape = tuple(mask.shape)
-    m = _frames_on_gpu(mask)
+    m = frames_on_gpu(mask)
     lib = _lib.load()
     N, H, W = m.shape
     dev = m.device
     with torch.cuda.device(dev):
         dist2 = torch.empty((N, H, W), dtype=torch.int32, device=dev)
         nearest = torch.empty((N, H, W), dtype=torch.int32, device=dev) if return_nearest else None
-        ws, nbytes = _workspace(lib, N, H, W, dev)
+        ws, nbytes = workspace(lib, "unet_distance_workspace_bytes", dev, N, H, W)
         _lib.check(lib.unet_distance_transform(m.data_ptr(), int(m.dtype == torch.int32), N, H, W, fgv,
                                                int(bool(invert)), dist2.data_ptr(), _lib.ptr(nearest), ws.data_ptr(),
                                                nbytes, _lib.stream_handle(dev)), "unet_distance_transform")
@@ -121,7 +82,7 @@ def grow_instances(labels, max_distance=None, within=None, within_value=None):
     Returns int32 labels of the same shape; the set of ids is unchanged (as
     ``skimage.segmentation.expand_labels``).  The input is not modified.
     """
-    labels = _as_frames(labels, "grow_instances: labels", (torch.int32,))
+    labels = as_frames(labels, "grow_instances: labels", (torch.int32,), _lib.DISTANCE_MAX_DIM)
     if max_distance is None:
         max_d2 = -1
     else:
@@ -132,20 +93,20 @@ def grow_instances(labels, max_distance=None, within=None, within_value=None):
     if within_value is not None and (within is None or not 0 <= int(within_value) <= 255):
         raise ValueError(f"within_value={within_value} needs within and must be in 0..255")
     if within is not None:
-        within = _as_frames(within, "grow_instances: within", (torch.uint8, torch.bool))
+        within = as_frames(within, "grow_instances: within", (torch.uint8, torch.bool), _lib.DISTANCE_MAX_DIM)
         if tuple(within.shape) != tuple(labels.shape):
             raise ValueError(f"grow_instances: within {tuple(within.shape)} and labels {tuple(labels.shape)} differ")
     shape = tuple(labels.shape)
-    lab = _frames_on_gpu(labels)
+    lab = frames_on_gpu(labels)
     dev = lab.device
     w = None
     if within is not None:
-        w = _frames_on_gpu(within.to(dev) if within.device != dev else within)
+        w = frames_on_gpu(within.to(dev) if within.device != dev else within)
     lib = _lib.load()
     N, H, W = lab.shape
     with torch.cuda.device(dev):
         out = torch.empty((N, H, W), dtype=torch.int32, device=dev)
-        ws, nbytes = _workspace(lib, N, H, W, dev)
+        ws, nbytes = workspace(lib, "unet_distance_workspace_bytes", dev, N, H, W)
         _lib.check(lib.unet_grow_instances(lab.data_ptr(), N, H, W, max_d2, _lib.ptr(w),
                                            -1 if within_value is None else int(within_value), out.data_ptr(),
                                            ws.data_ptr(), nbytes, _lib.stream_handle(dev)), "unet_grow_instances")

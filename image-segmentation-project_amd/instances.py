@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._frames import as_frames, frames_on_gpu, workspace
 
 STATS_COLUMNS = ("area", "sum_y", "sum_x", "y0", "x0", "y1", "x1")  # the last axis of the stats table
 assert len(STATS_COLUMNS) == _lib.INSTANCE_STATS
@@ -29,20 +30,7 @@ def _check_args(mask, connectivity, min_area, foreground, max_instances):
         raise ValueError(f"max_instances={max_instances} must be >= 1")
     if foreground is not None and not 0 <= int(foreground) <= 255:
         raise ValueError(f"foreground={foreground} is outside 0..255")
-    if isinstance(mask, np.ndarray):
-        if mask.dtype not in (np.uint8, np.bool_):
-            raise ValueError(f"label_instances: mask must be uint8 or bool, got {mask.dtype}")
-        mask = torch.from_numpy(np.ascontiguousarray(mask))
-    if not isinstance(mask, torch.Tensor):
-        raise ValueError(f"label_instances: mask must be a tensor or an array, got {type(mask).__name__}")
-    if mask.dtype not in (torch.uint8, torch.bool):
-        raise ValueError(f"label_instances: mask must be uint8 or bool, got {mask.dtype}")
-    if mask.dim() not in (2, 3, 4):
-        raise ValueError(f"label_instances: mask must be [H, W], [N, H, W] or [N, K, H, W], got {tuple(mask.shape)}")
-    if mask.numel() == 0:
-        raise ValueError("label_instances: empty mask")
-    if mask.shape[-2] * mask.shape[-1] >= 1 << 31:
-        raise ValueError(f"label_instances: H * W = {mask.shape[-2] * mask.shape[-1]} must be below 2^31")
+    mask = as_frames(mask, "label_instances: mask", (torch.uint8, torch.bool))
     return mask, (-1 if foreground is None else int(foreground))
 
 
@@ -73,27 +61,18 @@ def label_instances(mask, connectivity=1, min_area=0, fill_holes=False, foregrou
     if return_filled and not fill_holes:
         raise ValueError("return_filled=True needs fill_holes=True")
     min_area, max_instances = int(min_area), int(max_instances)
-    if not mask.is_cuda:
-        _lib.require_gpu()
-        mask = mask.cuda()
-    _lib.require_gpu(mask)
-    lib = _lib.load()
     shape = tuple(mask.shape)
-    H, W = shape[-2:]
     lead = shape[:-2]
-    m = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
-    m = m.reshape(-1, H, W).contiguous()
-    N = m.shape[0]
+    m = frames_on_gpu(mask)
+    lib = _lib.load()
+    N, H, W = m.shape
     dev = m.device
     with torch.cuda.device(dev):
         labels = torch.empty((N, H, W), dtype=torch.int32, device=dev)
         counts = torch.empty((N,), dtype=torch.int32, device=dev)
         stats = torch.empty((N, max_instances, _lib.INSTANCE_STATS), dtype=torch.int64, device=dev) if return_stats else None
         filled = torch.empty((N, H, W), dtype=torch.uint8, device=dev) if return_filled else None
-        nbytes = int(lib.unet_instances_workspace_bytes(N, H, W))
-        if nbytes <= 0:
-            _lib.check(1, "unet_instances_workspace_bytes")
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        ws, nbytes = workspace(lib, "unet_instances_workspace_bytes", dev, N, H, W)
         _lib.check(lib.unet_label_instances(m.data_ptr(), N, H, W, fgv, int(connectivity), int(bool(fill_holes)),
                                             min_area, max_instances, labels.data_ptr(), counts.data_ptr(),
                                             _lib.ptr(stats), _lib.ptr(filled), ws.data_ptr(), nbytes,

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._frames import as_frames, frames_on_gpu, workspace
 from .utils import EPS
 
 MATCH_COLUMNS = ("area", "partner", "intersection", "partner_area")  # the last axis of both tables
@@ -28,25 +29,6 @@ DEFAULT_THRESHOLDS = tuple(Fraction(10 + k, 20) for k in range(10))  # 0.5, 0.55
 
 InstanceMatch = collections.namedtuple("InstanceMatch", ("gt_table", "pred_table", "status"))
 InstanceMatchPairs = collections.namedtuple("InstanceMatch", ("gt_table", "pred_table", "status", "pairs"))
-
-
-def _as_labels(x, what):
-    """Validate an int32 label map; raises ValueError, touches no GPU."""
-    if isinstance(x, np.ndarray):
-        if x.dtype != np.int32:
-            raise ValueError(f"match_instances: {what} must be int32, got {x.dtype}")
-        x = torch.from_numpy(np.ascontiguousarray(x))
-    if not isinstance(x, torch.Tensor):
-        raise ValueError(f"match_instances: {what} must be a tensor or an array, got {type(x).__name__}")
-    if x.dtype != torch.int32:
-        raise ValueError(f"match_instances: {what} must be int32, got {x.dtype}")
-    if x.dim() not in (2, 3, 4):
-        raise ValueError(f"match_instances: {what} must be [H, W], [N, H, W] or [N, K, H, W], got {tuple(x.shape)}")
-    if x.numel() == 0:
-        raise ValueError(f"match_instances: {what} is empty")
-    if x.shape[-2] * x.shape[-1] >= 1 << 31:
-        raise ValueError(f"match_instances: H * W = {x.shape[-2] * x.shape[-1]} must be below 2^31")
-    return x
 
 
 def match_instances(pred, gt, max_instances=4096, max_pairs=None, return_pairs=False):
@@ -76,8 +58,8 @@ def match_instances(pred, gt, max_instances=4096, max_pairs=None, return_pairs=F
     them.  The inputs are not modified and nothing synchronises with the host;
     ``instance_metrics`` does.
     """
-    pred = _as_labels(pred, "pred")
-    gt = _as_labels(gt, "gt")
+    pred = as_frames(pred, "match_instances: pred", (torch.int32,))
+    gt = as_frames(gt, "match_instances: gt", (torch.int32,))
     if tuple(pred.shape) != tuple(gt.shape):
         raise ValueError(f"match_instances: pred {tuple(pred.shape)} and gt {tuple(gt.shape)} differ")
     if isinstance(max_instances, bool) or not 1 <= int(max_instances) <= MAX_ID:
@@ -93,24 +75,17 @@ def match_instances(pred, gt, max_instances=4096, max_pairs=None, return_pairs=F
         pred, gt = pred.cuda(), gt.cuda()
     elif pred.device != gt.device:
         pred, gt = (pred.to(gt.device), gt) if gt.is_cuda else (pred, gt.to(pred.device))
-    _lib.require_gpu(pred, gt)
+    lead = tuple(gt.shape)[:-2]
+    p, g = frames_on_gpu(pred), frames_on_gpu(gt)
     lib = _lib.load()
-    shape = tuple(gt.shape)
-    H, W = shape[-2:]
-    lead = shape[:-2]
-    p = pred.reshape(-1, H, W).contiguous()
-    g = gt.reshape(-1, H, W).contiguous()
-    N = g.shape[0]
+    N, H, W = g.shape
     dev = g.device
     with torch.cuda.device(dev):
         gt_table = torch.empty((N, max_instances, _lib.MATCH_COLS), dtype=torch.int64, device=dev)
         pred_table = torch.empty((N, max_instances, _lib.MATCH_COLS), dtype=torch.int64, device=dev)
         status = torch.empty((N, _lib.MATCH_STATUS), dtype=torch.int64, device=dev)
         pairs = torch.empty((N, max_pairs, 3), dtype=torch.int64, device=dev) if return_pairs else None
-        nbytes = int(lib.unet_match_workspace_bytes(N, max_instances, max_instances, max_pairs))
-        if nbytes <= 0:
-            _lib.check(1, "unet_match_workspace_bytes")
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        ws, nbytes = workspace(lib, "unet_match_workspace_bytes", dev, N, max_instances, max_instances, max_pairs)
         _lib.check(lib.unet_match_instances(g.data_ptr(), p.data_ptr(), N, H, W, max_instances, max_instances,
                                             max_pairs, gt_table.data_ptr(), pred_table.data_ptr(), status.data_ptr(),
                                             _lib.ptr(pairs), ws.data_ptr(), nbytes, _lib.stream_handle(dev)),

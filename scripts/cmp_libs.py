@@ -1,10 +1,12 @@
 """Bit-identity of one training step between two library builds: each build
 runs in its own process (UNET_HIP_LIB); the logits, every parameter gradient,
 every buffer after the step (running_mean / running_var / num_batches_tracked
-of each BN) and the logits of one eval() forward of the same input after the
-step (running statistics, eval fold) are saved and compared bit for bit; each
-build's plan workspace size is printed.  For refactors that must not change
-numerics (same summation orders, same expressions).
+of each BN) and the logits of one eval() forward of the same input (running
+statistics, eval fold) are saved and compared bit for bit; each build's plan
+workspace size is printed.  A second training step and that eval forward run
+under the plan's profiler: the ordered (launch name, kernel instance) lists of
+the two builds must be equal too.  For refactors that must not change numerics
+(same summation orders, same expressions) or launches.
 usage: python scripts/cmp_libs.py lib_a.so lib_b.so [--batch 4] [--size 256] [--attention]
                                   [--backbone resnet34|resnet50] [--width 1|2] [--fp8]"""
 import argparse
@@ -41,9 +43,13 @@ if args.child:
     res = {"logits": out.detach().cpu()}
     res.update({k: p.grad.detach().cpu() for k, p in m.named_parameters()})
     res.update({"buffer." + k: b.detach().cpu() for k, b in m.named_buffers()})
+    plan = m._last_plan
+    plan.profile(True)
+    pkg.get_loss_function({"loss_fn": "bce"})(m(x), y).backward()
     m.eval()
     with torch.no_grad():
         res["eval_logits"] = m(x).cpu()
+    res["launches"] = [(name, kernel) for name, _, _, kernel in plan.profile_report()]
     torch.save(res, args.child)
     sys.exit(0)
 
@@ -59,7 +65,13 @@ for i, lib in enumerate(args.libs):
 import torch  # noqa: E402
 
 a, b = (torch.load(p, weights_only=True) for p in outs)
+la, lb = a.pop("launches"), b.pop("launches")
+first = next((i for i, (u, v) in enumerate(zip(la, lb)) if u != v), None)
+if first is None and len(la) != len(lb):
+    first = min(len(la), len(lb))
+print(f"launches: {len(la)} vs {len(lb)}, " + ("same names and kernels in the same order" if first is None else
+                                              f"first difference at {first}: {la[first:first + 1]} vs {lb[first:first + 1]}"))
 diff = [k for k in a if not torch.equal(a[k], b[k])]
 groups = {g: sum(k.startswith(g) for k in a) for g in ("buffer.", "eval_logits")}
 print(f"{len(a)} tensors compared ({groups['buffer.']} buffers, {groups['eval_logits']} eval logits), {len(diff)} differ" + (": " + ", ".join(diff) if diff else ""))
-sys.exit(1 if diff else 0)
+sys.exit(1 if diff or first is not None else 0)
