@@ -9,6 +9,9 @@ and tiled whole-frame inference on frames of any size (``predict``) with
 instance labelling of the predicted masks (``label_instances``), exact distance
 maps and growth of the instances (``distance_transform``, ``grow_instances``) and
 their scores against a ground truth (``match_instances``, ``instance_metrics``),
+and the training targets of that scheme from a ground-truth instance map
+(``boundary_targets``, ``border_weight_map``, ``nearest_two_instances``; per-pixel
+weights in ``CrossEntropyLoss`` / ``SoftmaxComboLoss``),
 computed by hand-written gfx950 HIP kernels in ``libunet_hip.so`` (C ABI:
 ``include/unet_hip.h``).  The directory name carries hyphens, so import it with
 ``importlib.import_module("image-segmentation-project_amd")``.
@@ -27,6 +30,7 @@ from .dataset import CellAugmenter, CellSegmentationDataset, prepare_data, prepr
 from .predict import predict, tile_origins  # noqa: F401
 from .instances import instance_properties, label_instances  # noqa: F401
 from .distance import distance_transform, grow_instances  # noqa: F401
+from .weights import border_weight_map, boundary_targets, nearest_two_instances  # noqa: F401
 from .match import InstanceMatch, instance_metrics, match_instances  # noqa: F401
 from . import ddp  # noqa: F401
 from . import optim  # noqa: F401

@@ -25,6 +25,7 @@ TILE_MAX = 1024  # UNET_TILE_MAX: largest tile of unet_tile_gather / unet_tile_b
 INSTANCE_STATS = 7  # UNET_INSTANCE_STATS: area, sum_y, sum_x, y0, x0, y1, x1
 DISTANCE_NONE = 2147483647  # UNET_DISTANCE_NONE: dist2 of a frame without a site
 DISTANCE_MAX_DIM = 32768  # UNET_DISTANCE_MAX_DIM: largest H and W of the distance transform
+TWO_NEAREST_MAX_DIM = 4096  # UNET_TWO_NEAREST_MAX_DIM: largest H and W of the two-nearest transform / border weights
 MATCH_COLS = 4  # UNET_MATCH_COLS: area, partner, intersection, partner_area
 MATCH_STATUS = 5  # UNET_MATCH_STATUS: n_gt, n_pred, n_pairs, dropped, out_of_range
 
@@ -124,6 +125,12 @@ SIGNATURES = {
                                           c_float, c_float, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "unet_softmax_loss_backward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int, c_int,
                                            c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "unet_softmax_loss_forward_pw": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p,
+                                             c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_int64, c_void_p,
+                                             c_void_p]),
+    "unet_softmax_loss_backward_pw": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_void_p,
+                                              c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,
+                                              c_void_p]),
     "unet_confusion_matrix": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_int, c_void_p, c_void_p,
                                       c_int64, c_void_p]),
     "unet_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float,
@@ -179,6 +186,11 @@ SIGNATURES = {
     "unet_distance_transform": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p] * 3 + [c_int64, c_void_p]),
     "unet_grow_instances": (c_int, [c_void_p] + [c_int] * 3 + [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64,
                                                                 c_void_p]),
+    "unet_two_nearest_workspace_bytes": (c_int64, [c_int] * 3),
+    "unet_two_nearest_instances": (c_int, [c_void_p] + [c_int] * 3 + [c_int64] + [c_void_p] * 3 + [c_int64, c_void_p]),
+    "unet_border_weights": (c_int, [c_void_p] + [c_int] * 3 + [c_float, c_float, c_int64, c_void_p, c_void_p, c_int,
+                                                                c_void_p, c_void_p, c_int64, c_void_p]),
+    "unet_boundary_targets": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p, c_void_p]),
     "unet_match_workspace_bytes": (c_int64, [c_int] * 4),
     "unet_match_instances": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p] * 5 + [c_int64, c_void_p]),
     "unet_maxpool_fwd": (c_int,[c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),

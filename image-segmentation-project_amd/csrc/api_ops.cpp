@@ -150,6 +150,40 @@ int unet_softmax_loss_backward(const float* logits, const void* labels, int labe
   return 0;
 }
 
+static bool softmax_pw_ok(const char* fn, int kind, const float* pixel_weights) {
+  if (kind == LOSS_DICE && pixel_weights)
+    return errf("%s: pixel weights apply to the CE term; kind 1 (dice) takes none", fn);
+  return true;
+}
+
+int unet_softmax_loss_forward_pw(const float* logits, const void* labels, int label_dtype, int N, int K, int64_t HW,
+                                 const float* class_weights, const float* pixel_weights, int ignore_index, int kind,
+                                 float alpha, float smooth, double* sums, double* scratch, int64_t scratch_len,
+                                 float* loss_out, hipStream_t stream) {
+  const char* fn = "unet_softmax_loss_forward_pw";
+  if (!softmax_args_ok(fn, logits, labels, label_dtype, N, K, HW) || !softmax_kind_ok(fn, kind, class_weights) ||
+      !softmax_pw_ok(fn, kind, pixel_weights) || !softmax_scratch_ok(fn, scratch, scratch_len))
+    return 1;
+  if (!sums || !loss_out) { set_err("unet_softmax_loss_forward_pw: sums / loss_out is null"); return 1; }
+  const SoftmaxArgs a{logits, labels, label_dtype, N, K, HW, class_weights, ignore_index, pixel_weights};
+  CK(launch_softmax_loss_sums(a, kind, alpha, smooth, sums, scratch, loss_out, stream));
+  return 0;
+}
+
+int unet_softmax_loss_backward_pw(const float* logits, const void* labels, int label_dtype, int N, int K, int64_t HW,
+                                  const float* class_weights, const float* pixel_weights, int ignore_index, int kind,
+                                  float alpha, float smooth, const double* sums, const float* grad_scale,
+                                  float* dlogits, hipStream_t stream) {
+  const char* fn = "unet_softmax_loss_backward_pw";
+  if (!softmax_args_ok(fn, logits, labels, label_dtype, N, K, HW) || !softmax_kind_ok(fn, kind, class_weights) ||
+      !softmax_pw_ok(fn, kind, pixel_weights))
+    return 1;
+  if (!sums || !dlogits) { set_err("unet_softmax_loss_backward_pw: sums / dlogits is null"); return 1; }
+  const SoftmaxArgs a{logits, labels, label_dtype, N, K, HW, class_weights, ignore_index, pixel_weights};
+  CK(launch_softmax_loss_grad(a, kind, alpha, smooth, sums, grad_scale, dlogits, stream));
+  return 0;
+}
+
 int unet_confusion_matrix(const float* logits, const void* labels, int label_dtype, int N, int K, int64_t HW,
                           int ignore_index, long long* cm, double* scratch, int64_t scratch_len,
                           hipStream_t stream) {
@@ -783,6 +817,69 @@ int unet_grow_instances(const int32_t* labels, int N, int H, int W, int64_t max_
   const DistArgs a{labels, 1, N, H, W, -1, 1, nullptr, nullptr, max_dist2, within, within_value, out, workspace,
                    workspace_bytes};
   CK(launch_distance(a, stream));
+  return 0;
+}
+
+// ---- two nearest distinct instances, border weights, boundary targets (weights.hip) ----
+static_assert(kTwoMaxDim == UNET_TWO_NEAREST_MAX_DIM, "size limit of the header");
+
+static bool two_shape_ok(const char* fn, int N, int H, int W) {
+  if (N > 0 && H > 0 && W > 0 && H <= kTwoMaxDim && W <= kTwoMaxDim) return true;
+  return errf("%s: N = %d, H = %d, W = %d must be positive with H, W <= %d", fn, N, H, W, kTwoMaxDim);
+}
+
+static bool two_workspace_ok(const char* fn, int N, int H, int W, const void* workspace, int64_t bytes) {
+  return workspace_ok(fn, "unet_two_nearest_workspace_bytes", workspace, bytes, two_nearest_workspace_bytes(N, H, W));
+}
+
+int64_t unet_two_nearest_workspace_bytes(int N, int H, int W) {
+  if (!two_shape_ok("unet_two_nearest_workspace_bytes", N, H, W)) return 0;
+  return two_nearest_workspace_bytes(N, H, W);
+}
+
+int unet_two_nearest_instances(const int32_t* labels, int N, int H, int W, int64_t max_dist2, int32_t* dist2,
+                               int32_t* ids, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
+  const char* fn = "unet_two_nearest_instances";
+  if (!labels) { set_err("unet_two_nearest_instances: labels is null"); return 1; }
+  if (!dist2 && !ids) { set_err("unet_two_nearest_instances: dist2 and ids are both null"); return 1; }
+  if (!two_shape_ok(fn, N, H, W) || !two_workspace_ok(fn, N, H, W, workspace, workspace_bytes)) return 1;
+  const TwoArgs a{labels, N, H, W, max_dist2, dist2, ids, 0.f, 0.f, nullptr, nullptr, 0, nullptr, workspace,
+                  workspace_bytes};
+  CK(launch_two_nearest(a, stream));
+  return 0;
+}
+
+int unet_border_weights(const int32_t* labels, int N, int H, int W, float w0, float sigma, int64_t max_dist2,
+                        const uint8_t* classes, const float* class_weights, int K, float* out, void* workspace,
+                        int64_t workspace_bytes, hipStream_t stream) {
+  const char* fn = "unet_border_weights";
+  if (!labels || !out) { set_err("unet_border_weights: labels / out is null"); return 1; }
+  if (!two_shape_ok(fn, N, H, W)) return 1;
+  if (!(w0 >= 0.f) || !(sigma > 0.f)) {
+    errf("%s: w0 = %g must be >= 0 and sigma = %g > 0", fn, (double)w0, (double)sigma);
+    return 1;
+  }
+  if ((classes != nullptr) != (class_weights != nullptr) || (classes && K <= 0)) {
+    errf("%s: classes and class_weights go together, with K = %d > 0", fn, K);
+    return 1;
+  }
+  if (!two_workspace_ok(fn, N, H, W, workspace, workspace_bytes)) return 1;
+  const TwoArgs a{labels, N, H, W, max_dist2, nullptr, nullptr, w0, sigma, classes, class_weights, K, out, workspace,
+                  workspace_bytes};
+  CK(launch_two_nearest(a, stream));
+  return 0;
+}
+
+int unet_boundary_targets(const int32_t* labels, int N, int H, int W, int connectivity, uint8_t* classes,
+                          hipStream_t stream) {
+  const char* fn = "unet_boundary_targets";
+  if (!labels || !classes) { set_err("unet_boundary_targets: labels / classes is null"); return 1; }
+  if (!distance_shape_ok(fn, N, H, W)) return 1;
+  if (connectivity != 1 && connectivity != 2) {
+    errf("%s: connectivity = %d must be 1 (4 neighbours) or 2 (8)", fn, connectivity);
+    return 1;
+  }
+  CK(launch_boundary_targets(labels, N, H, W, connectivity, classes, stream));
   return 0;
 }
 

@@ -446,6 +446,7 @@ constexpr int kSmSums = 4 + 3 * kSmMaxK;
 struct SoftmaxArgs {
   const float* logits; const void* labels; int label_dtype; int N, K; int64_t HW;
   const float* class_weights; int ignore_index;
+  const float* pixel_weights = nullptr;  // [N][HW] or null: the _pw entries (a compile-time switch of both kernels)
 };
 // part: kSmSums * kSmSlots doubles (value-major per-block partials); kind: LOSS_BCE = CE, LOSS_DICE, LOSS_COMBO
 hipError_t launch_softmax_loss_sums(const SoftmaxArgs& a, int kind, float alpha, float smooth, double* sums,
@@ -549,6 +550,29 @@ struct DistArgs {
 int64_t distance_workspace_bytes(int N, int H, int W);
 // hipErrorInvalidValue (nothing launched) on a null buffer, a bad argument or a short workspace
 hipError_t launch_distance(const DistArgs& a, hipStream_t st);
+
+// two nearest distinct instances, border weight map, boundary targets (weights.hip)
+constexpr int kTwoMaxDim = 4096;  // H, W <= this: a row's two candidates with their labels are 12 W bytes of LDS
+struct TwoArgs {
+  const int* labels;     // [N][H][W]; sites are labels > 0
+  int N, H, W;
+  int64_t max_dist2;     // < 0: unlimited
+  int* dist2;            // [N][2][H][W] or null
+  int* ids;              // [N][2][H][W] or null
+  // border weights (out != null): dist2 / ids are unused
+  float w0, sigma;
+  const uint8_t* classes;      // [N][H][W] or null
+  const float* class_weights;  // K floats or null (both or neither)
+  int K;
+  float* out;            // [N][H][W]
+  void* workspace; int64_t workspace_bytes;
+};
+// 0 for N, H, W <= 0 or H, W > kTwoMaxDim
+int64_t two_nearest_workspace_bytes(int N, int H, int W);
+// hipErrorInvalidValue (nothing launched) on a null buffer, a bad argument or a short workspace
+hipError_t launch_two_nearest(const TwoArgs& a, hipStream_t st);
+hipError_t launch_boundary_targets(const int* labels, int N, int H, int W, int connectivity, uint8_t* classes,
+                                   hipStream_t st);
 
 // matching of two instance label maps (match.hip): pair histogram, areas, the
 // partner of highest IoU of every instance on both sides, the list of pairs

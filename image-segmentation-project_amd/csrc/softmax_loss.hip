@@ -138,12 +138,15 @@ struct SmAcc {
   // branch-free (selects, not products: a non-finite logit of an ignored pixel
   // must not reach the sums): divergent per-pixel branches cost more than the
   // softmax of the few ignored pixels
-  __device__ __forceinline__ void add(const float (&z)[K], int y, const float* sw) {
+  // PW: the pixel's own weight pw multiplies the class weight (a compile-time
+  // switch: the unweighted instance is the code it was)
+  template <bool PW = false>
+  __device__ __forceinline__ void add(const float (&z)[K], int y, const float* sw, float pw = 1.f) {
     const bool ok = y >= 0;
     float p[K], nll, S, ru;
     int km;
     softmax_px<K>(z, y, p, nll, km, S, ru);
-    const float w = sw[ok ? y : 0];
+    const float w = PW ? sw[ok ? y : 0] * pw : sw[ok ? y : 0];
     ce += ok ? w * nll : 0.f;
     wden += ok ? w : 0.f;
     nvalid += ok ? 1.f : 0.f;
@@ -210,10 +213,11 @@ __device__ __forceinline__ double wave_sums_transposed(const SmAcc<K>& acc, int 
 // registers and measured slower at every K (16 x K x 512 x 512, K = 2 / 4 / 8 /
 // 16: 27.8 / 36.7 / 61.0 / 86.7 us, and 127 to 138 us once the K = 16 instance
 // passes 256 registers, against 24.7 / 29.4 / 51.8 / 79.0 us).
-template <int K>
+template <int K, bool PW>
 __global__ void __launch_bounds__(kSmNT) softmax_loss_sums_kernel(const float* __restrict__ x,
                                                                   const void* __restrict__ lab, int dt, int N,
-                                                                  int64_t HW, const float* __restrict__ cw, int ign,
+                                                                  int64_t HW, const float* __restrict__ cw,
+                                                                  const float* __restrict__ pw, int ign,
                                                                   double* __restrict__ part) {
   constexpr int NS = 4 + 3 * K;
   __shared__ float sw[K];
@@ -230,7 +234,8 @@ __global__ void __launch_bounds__(kSmNT) softmax_loss_sums_kernel(const float* _
       float z[K];
 #pragma unroll
       for (int k = 0; k < K; ++k) z[k] = xn[(size_t)k * HW + i];
-      acc.add(z, load_class(lab, dt, lbase + i, K, ign), sw);
+      if (PW) acc.template add<true>(z, load_class(lab, dt, lbase + i, K, ign), sw, pw[lbase + i]);
+      else acc.add(z, load_class(lab, dt, lbase + i, K, ign), sw);
     }
   }
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -292,12 +297,14 @@ struct SmGrad {
   float c[K], b[K];  // already scaled by g * wd
   float gce;         // g * wb / w_den
   bool dice;
-  __device__ __forceinline__ void px(const float (&z)[K], int y, const float* sw, float (&d)[K]) const {
+  template <bool PW = false>
+  __device__ __forceinline__ void px(const float (&z)[K], int y, const float* sw, float (&d)[K],
+                                     float pw = 1.f) const {
     const bool ok = y >= 0;  // branch-free as SmAcc::add; an ignored pixel's channels are selected to 0 at the end
     float p[K], nll, S, ru;
     int km;
     softmax_px<K>(z, y, p, nll, km, S, ru);
-    const float wy = gce * sw[ok ? y : 0];
+    const float wy = PW ? gce * (sw[ok ? y : 0] * pw) : gce * sw[ok ? y : 0];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       const float pm1 = k == km ? -S * ru : p[k] - 1.f;
@@ -321,10 +328,11 @@ struct SmGrad {
   }
 };
 
-template <int K>
+template <int K, bool PW>
 __global__ void __launch_bounds__(kSmNT) softmax_loss_grad_kernel(const float* __restrict__ x,
                                                                   const void* __restrict__ lab, int dt, int N,
-                                                                  int64_t HW, const float* __restrict__ cw, int ign,
+                                                                  int64_t HW, const float* __restrict__ cw,
+                                                                  const float* __restrict__ pw, int ign,
                                                                   int vec, const double* __restrict__ s, int kind,
                                                                   float alpha, float smooth,
                                                                   const float* __restrict__ gscale,
@@ -357,6 +365,7 @@ __global__ void __launch_bounds__(kSmNT) softmax_loss_grad_kernel(const float* _
       const int64_t nq = HW >> 2;
       for (int64_t q = tid; q < nq; q += U * stride) {
         float zv[U][K][4];
+        float wv[PW ? U : 1][4];  // the pixels' weights, loaded as the logits are
         int yc[U][4];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -364,6 +373,15 @@ __global__ void __launch_bounds__(kSmNT) softmax_loss_grad_kernel(const float* _
           if (j < nq) {
             load_quad<K>(xn, HW, j, vec, zv[u]);
             load_classes4(lab, dt, lbase + 4 * j, K, ign, vec, yc[u]);
+            if (PW) {
+              const float* p = pw + lbase + 4 * j;
+              if (vec) {
+                const float4 v = *reinterpret_cast<const float4*>(p);
+                wv[PW ? u : 0][0] = v.x; wv[PW ? u : 0][1] = v.y; wv[PW ? u : 0][2] = v.z; wv[PW ? u : 0][3] = v.w;
+              } else {
+                wv[PW ? u : 0][0] = p[0]; wv[PW ? u : 0][1] = p[1]; wv[PW ? u : 0][2] = p[2]; wv[PW ? u : 0][3] = p[3];
+              }
+            }
           }
         }
 #pragma unroll
@@ -376,7 +394,8 @@ __global__ void __launch_bounds__(kSmNT) softmax_loss_grad_kernel(const float* _
             float z[K], d[K];
 #pragma unroll
             for (int k = 0; k < K; ++k) z[k] = zv[u][k][c];
-            G.px(z, yc[u][c], sw, d);
+            if (PW) G.template px<true>(z, yc[u][c], sw, d, wv[PW ? u : 0][c]);
+            else G.px(z, yc[u][c], sw, d);
 #pragma unroll
             for (int k = 0; k < K; ++k) dv[k][c] = d[k];
           }
@@ -396,7 +415,8 @@ __global__ void __launch_bounds__(kSmNT) softmax_loss_grad_kernel(const float* _
       float z[K], d[K];
 #pragma unroll
       for (int k = 0; k < K; ++k) z[k] = xn[(size_t)k * HW + i];
-      G.px(z, load_class(lab, dt, lbase + i, K, ign), sw, d);
+      if (PW) G.template px<true>(z, load_class(lab, dt, lbase + i, K, ign), sw, d, pw[lbase + i]);
+      else G.px(z, load_class(lab, dt, lbase + i, K, ign), sw, d);
 #pragma unroll
       for (int k = 0; k < K; ++k) dn[(size_t)k * HW + i] = d[k];
     }
@@ -506,15 +526,26 @@ bool sm_args_ok(const SoftmaxArgs& a) {
 
 template <int K>
 void run_sums(dim3 grid, hipStream_t st, const SoftmaxArgs& a, double* part) {
-  softmax_loss_sums_kernel<K><<<grid, dim3(kSmNT), 0, st>>>(a.logits, a.labels, a.label_dtype, a.N, a.HW,
-                                                            a.class_weights, a.ignore_index, part);
+  if (a.pixel_weights)
+    softmax_loss_sums_kernel<K, true><<<grid, dim3(kSmNT), 0, st>>>(a.logits, a.labels, a.label_dtype, a.N, a.HW,
+                                                                    a.class_weights, a.pixel_weights,
+                                                                    a.ignore_index, part);
+  else
+    softmax_loss_sums_kernel<K, false><<<grid, dim3(kSmNT), 0, st>>>(a.logits, a.labels, a.label_dtype, a.N, a.HW,
+                                                                     a.class_weights, nullptr, a.ignore_index, part);
 }
 template <int K>
 void run_grad(dim3 grid, hipStream_t st, const SoftmaxArgs& a, int vec, const double* sums, int kind, float alpha,
               float smooth, const float* gscale, float* dl) {
-  softmax_loss_grad_kernel<K><<<grid, dim3(kSmNT), 0, st>>>(a.logits, a.labels, a.label_dtype, a.N, a.HW,
-                                                            a.class_weights, a.ignore_index, vec, sums, kind, alpha,
-                                                            smooth, gscale, dl);
+  if (a.pixel_weights)
+    softmax_loss_grad_kernel<K, true><<<grid, dim3(kSmNT), 0, st>>>(a.logits, a.labels, a.label_dtype, a.N, a.HW,
+                                                                    a.class_weights, a.pixel_weights,
+                                                                    a.ignore_index, vec, sums, kind, alpha, smooth,
+                                                                    gscale, dl);
+  else
+    softmax_loss_grad_kernel<K, false><<<grid, dim3(kSmNT), 0, st>>>(a.logits, a.labels, a.label_dtype, a.N, a.HW,
+                                                                     a.class_weights, nullptr, a.ignore_index, vec,
+                                                                     sums, kind, alpha, smooth, gscale, dl);
 }
 template <int K>
 void run_confusion(dim3 grid, hipStream_t st, const SoftmaxArgs& a, int vec, unsigned* part) {
@@ -538,7 +569,7 @@ void run_confusion(dim3 grid, hipStream_t st, const SoftmaxArgs& a, int vec, uns
 
 hipError_t launch_softmax_loss_sums(const SoftmaxArgs& a, int kind, float alpha, float smooth, double* sums,
                                     double* part, float* out, hipStream_t st) {
-  if (!sm_args_ok(a) || !sums || !part || !out) return hipErrorInvalidValue;
+  if (!sm_args_ok(a) || !sums || !part || !out || (kind == LOSS_DICE && a.pixel_weights)) return hipErrorInvalidValue;
   const dim3 grid = sm_grid(a, kSmNT, kSmSlots);
   SM_DISPATCH(a.K, run_sums, grid, st, a, part)
   hipError_t e = hipGetLastError();
@@ -550,9 +581,12 @@ hipError_t launch_softmax_loss_sums(const SoftmaxArgs& a, int kind, float alpha,
 
 hipError_t launch_softmax_loss_grad(const SoftmaxArgs& a, int kind, float alpha, float smooth, const double* sums,
                                     const float* gscale, float* dl, hipStream_t st) {
-  if (!sm_args_ok(a) || !sums || !dl) return hipErrorInvalidValue;
+  if (!sm_args_ok(a) || !sums || !dl || (kind == LOSS_DICE && a.pixel_weights)) return hipErrorInvalidValue;
   const dim3 grid = sm_grid(a, kSmNT, 4096);
-  const int vec = sm_vec_ok(a) && (reinterpret_cast<uintptr_t>(dl) & 15) == 0 ? 1 : 0;
+  const int vec = sm_vec_ok(a) && (reinterpret_cast<uintptr_t>(dl) & 15) == 0 &&
+                          (reinterpret_cast<uintptr_t>(a.pixel_weights) & 15) == 0
+                      ? 1
+                      : 0;
   SM_DISPATCH(a.K, run_grad, grid, st, a, vec, sums, kind, alpha, smooth, gscale, dl)
   return hipGetLastError();
 }

@@ -113,6 +113,20 @@ def softmax_inputs(logits, labels):
     return n, k, h * w, labels
 
 
+def pixel_weight_input(pixel_weights, n, h, w):
+    """Validate per-pixel loss weights (a float tensor ``[N,H,W]`` or ``[N,1,H,W]``)
+    against the logits' shape and return them as ``[N,H,W]``.  Raises
+    ``ValueError``; runs before any GPU is touched."""
+    if not isinstance(pixel_weights, torch.Tensor) or not pixel_weights.is_floating_point():
+        raise ValueError("pixel_weights must be a float tensor [N,H,W] or [N,1,H,W]")
+    if pixel_weights.dim() == 4 and pixel_weights.shape[1] == 1:
+        pixel_weights = pixel_weights[:, 0]
+    if tuple(pixel_weights.shape) != (n, h, w):
+        raise ValueError(f"pixel_weights {tuple(pixel_weights.shape)} do not match the logits: expected "
+                         f"[{n},{h},{w}] or [{n},1,{h},{w}]")
+    return pixel_weights
+
+
 def _class_weights(weight, k):
     if weight is None:
         return None
@@ -124,9 +138,13 @@ def _class_weights(weight, k):
 
 class _SoftmaxLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, labels, weight, kind, alpha, smooth, ignore_index):
+    def forward(ctx, logits, labels, weight, kind, alpha, smooth, ignore_index, pixel_weights=None):
         n, k, hw, labels = softmax_inputs(logits, labels)
         weight = _class_weights(weight, k)
+        if pixel_weights is not None:
+            if kind == DICE:
+                raise ValueError("pixel weights apply to the cross-entropy term; SoftmaxDiceLoss takes none")
+            pixel_weights = pixel_weight_input(pixel_weights, n, logits.shape[2], logits.shape[3])
         _lib.require_gpu(logits)
         lib = _lib.load()
         x = logits.contiguous().float()
@@ -134,26 +152,44 @@ class _SoftmaxLoss(torch.autograd.Function):
         w = None if weight is None else weight.to(x.device).contiguous()
         sums, scratch = _lib.softmax_buffers(x.device)
         out = torch.empty((), dtype=torch.float32, device=x.device)
-        _lib.check(lib.unet_softmax_loss_forward(
-            x.data_ptr(), y.data_ptr(), _lib.LABEL_DTYPES[y.dtype], n, k, hw, _lib.ptr(w), int(ignore_index), kind,
-            float(alpha), float(smooth), sums.data_ptr(), scratch.data_ptr(), scratch.numel(), out.data_ptr(),
-            _lib.stream_handle(x.device)), "unet_softmax_loss_forward")
-        ctx.save_for_backward(x, y, sums, *([] if w is None else [w]))
+        if pixel_weights is None:
+            pw = None
+            _lib.check(lib.unet_softmax_loss_forward(
+                x.data_ptr(), y.data_ptr(), _lib.LABEL_DTYPES[y.dtype], n, k, hw, _lib.ptr(w), int(ignore_index),
+                kind, float(alpha), float(smooth), sums.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                out.data_ptr(), _lib.stream_handle(x.device)), "unet_softmax_loss_forward")
+        else:
+            pw = pixel_weights.detach().to(x.device).contiguous().float()
+            _lib.check(lib.unet_softmax_loss_forward_pw(
+                x.data_ptr(), y.data_ptr(), _lib.LABEL_DTYPES[y.dtype], n, k, hw, _lib.ptr(w), pw.data_ptr(),
+                int(ignore_index), kind, float(alpha), float(smooth), sums.data_ptr(), scratch.data_ptr(),
+                scratch.numel(), out.data_ptr(), _lib.stream_handle(x.device)), "unet_softmax_loss_forward_pw")
+        # the tensors of backward in a fixed order: x, y, sums, then the class weights and the pixel weights if any
+        ctx.save_for_backward(x, y, sums, *([] if w is None else [w]), *([] if pw is None else [pw]))
+        ctx.has = (w is not None, pw is not None)
         ctx.cfg = (n, k, hw, kind, float(alpha), float(smooth), int(ignore_index))
         ctx.in_shape, ctx.in_dtype = logits.shape, logits.dtype
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        x, y, sums, *w = ctx.saved_tensors
+        x, y, sums, *rest = ctx.saved_tensors
+        w = rest.pop(0) if ctx.has[0] else None
+        pw = rest.pop(0) if ctx.has[1] else None
         n, k, hw, kind, alpha, smooth, ignore_index = ctx.cfg
         g = grad_out.contiguous().float()
         dl = torch.empty_like(x)
-        _lib.check(_lib.load().unet_softmax_loss_backward(
-            x.data_ptr(), y.data_ptr(), _lib.LABEL_DTYPES[y.dtype], n, k, hw, _lib.ptr(w[0] if w else None),
-            ignore_index, kind, alpha, smooth, sums.data_ptr(), g.data_ptr(), dl.data_ptr(),
-            _lib.stream_handle(x.device)), "unet_softmax_loss_backward")
-        return dl.view(ctx.in_shape).to(ctx.in_dtype), None, None, None, None, None, None
+        if pw is None:
+            _lib.check(_lib.load().unet_softmax_loss_backward(
+                x.data_ptr(), y.data_ptr(), _lib.LABEL_DTYPES[y.dtype], n, k, hw, _lib.ptr(w),
+                ignore_index, kind, alpha, smooth, sums.data_ptr(), g.data_ptr(), dl.data_ptr(),
+                _lib.stream_handle(x.device)), "unet_softmax_loss_backward")
+        else:
+            _lib.check(_lib.load().unet_softmax_loss_backward_pw(
+                x.data_ptr(), y.data_ptr(), _lib.LABEL_DTYPES[y.dtype], n, k, hw, _lib.ptr(w), pw.data_ptr(),
+                ignore_index, kind, alpha, smooth, sums.data_ptr(), g.data_ptr(), dl.data_ptr(),
+                _lib.stream_handle(x.device)), "unet_softmax_loss_backward_pw")
+        return dl.view(ctx.in_shape).to(ctx.in_dtype), None, None, None, None, None, None, None
 
 
 class _SoftmaxModule(nn.Module):
@@ -168,10 +204,16 @@ class _SoftmaxModule(nn.Module):
         self.ignore_index = int(ignore_index)
         self.register_buffer("weight", _class_weights(weight, None))
 
-    def forward(self, pred, target):
+    def forward(self, pred, target, pixel_weights=None):
+        """``pixel_weights``: a float tensor ``[N,H,W]`` or ``[N,1,H,W]`` (finite, >= 0; moved to
+        the logits' device), or ``None``.  A valid pixel then weighs ``weight[y] * pixel_weights[p]``
+        in the cross-entropy term (numerator, denominator and gradient); the Dice term is unweighted."""
         if self.weight is not None and isinstance(pred, torch.Tensor) and self.weight.device != pred.device:
             self.weight = self.weight.to(pred.device)
-        return _SoftmaxLoss.apply(pred, target, self.weight, self.kind, self.alpha, self.smooth, self.ignore_index)
+        if pixel_weights is not None and self.kind == DICE:
+            raise ValueError("pixel weights apply to the cross-entropy term; SoftmaxDiceLoss takes none")
+        return _SoftmaxLoss.apply(pred, target, self.weight, self.kind, self.alpha, self.smooth, self.ignore_index,
+                                  pixel_weights)
 
 
 class CrossEntropyLoss(_SoftmaxModule):

@@ -69,16 +69,26 @@ def _finish(records, with_loss_key: bool) -> Dict:
     return out
 
 
+def _criterion_call(criterion, outputs, masks, weights, device):
+    """criterion(outputs, masks), with the batch's third entry (if any) as pixel_weights"""
+    if not weights:
+        return criterion(outputs, masks)
+    if len(weights) != 1:
+        raise ValueError(f"a batch is (images, masks) or (images, masks, pixel_weights), got {2 + len(weights)} entries")
+    return criterion(outputs, masks, pixel_weights=weights[0].to(device, non_blocking=True))
+
+
 def train_epoch(model: torch.nn.Module, loader, optimizer: torch.optim.Optimizer, criterion: torch.nn.Module,
                 device: torch.device) -> Dict:
-    """train.py:17-68."""
+    """train.py:17-68.  A batch is ``(images, masks)`` or ``(images, masks, pixel_weights)``;
+    the weights go to the criterion as ``pixel_weights=`` (``CrossEntropyLoss`` / ``SoftmaxComboLoss``)."""
     model.train()
     records = []
-    for images, masks in loader:
+    for images, masks, *weights in loader:
         images = images.to(device, non_blocking=True)
         masks = masks.to(device, non_blocking=True)
         outputs = model(images)
-        loss = criterion(outputs, masks)
+        loss = _criterion_call(criterion, outputs, masks, weights, device)
         optimizer.zero_grad()
         loss.backward()
         optimizer.step()
@@ -88,15 +98,15 @@ def train_epoch(model: torch.nn.Module, loader, optimizer: torch.optim.Optimizer
 
 
 def evaluate(model: torch.nn.Module, loader, device: torch.device, criterion: torch.nn.Module) -> Dict:
-    """train.py:71-112 (eval-mode BN, no grad)."""
+    """train.py:71-112 (eval-mode BN, no grad); batches of two or three as ``train_epoch``."""
     model.eval()
     records = []
     with torch.no_grad():
-        for images, masks in loader:
+        for images, masks, *weights in loader:
             images = images.to(device, non_blocking=True)
             masks = masks.to(device, non_blocking=True)
             outputs = model(images)
-            loss = criterion(outputs, masks)
+            loss = _criterion_call(criterion, outputs, masks, weights, device)
             records.append(_batch_record(outputs, masks, loss, images.size(0), criterion))
     return _finish(records, with_loss_key=True)
 
@@ -172,11 +182,16 @@ def _is_frames(x) -> bool:
 
 
 class TensorLoader:
-    """Minimal in-memory replacement for ``prepare_data`` (dataset.py:121-138)."""
+    """Minimal in-memory replacement for ``prepare_data`` (dataset.py:121-138).
+    With ``weights`` (per-pixel loss weights, one map per image) it yields
+    ``(images, masks, weights)`` triples."""
 
-    def __init__(self, images, masks, batch_size, shuffle=False, seed=0):
+    def __init__(self, images, masks, batch_size, shuffle=False, seed=0, weights=None):
         self.images = torch.as_tensor(images)
         self.masks = torch.as_tensor(masks)
+        self.weights = None if weights is None else torch.as_tensor(weights)
+        if self.weights is not None and len(self.weights) != len(self.images):
+            raise ValueError(f"{len(self.weights)} weight maps for {len(self.images)} images")
         self.batch_size = batch_size
         self.shuffle = shuffle
         self.gen = torch.Generator().manual_seed(seed)
@@ -189,7 +204,10 @@ class TensorLoader:
         order = torch.randperm(n, generator=self.gen) if self.shuffle else torch.arange(n)
         for i in range(0, n, self.batch_size):
             idx = order[i:i + self.batch_size]
-            yield self.images[idx], self.masks[idx]
+            if self.weights is None:
+                yield self.images[idx], self.masks[idx]
+            else:
+                yield self.images[idx], self.masks[idx], self.weights[idx]
 
 
 def train_model(model, train_images, train_masks, val_images, val_masks, criterion, optimizer,

@@ -20,6 +20,9 @@
  *   unet_distance_transform / unet_grow_instances   exact Euclidean distance and nearest-site
  *                        transform of masks and label maps, nearest-label growth of instances
  *   unet_match_instances IoU tables of predicted instances against a ground truth label map
+ *   unet_two_nearest_instances / unet_border_weights / unet_boundary_targets   training targets
+ *                        for touching cells from a ground-truth instance map; unet_softmax_loss_*_pw
+ *                        take the weight map as per-pixel weights of the cross-entropy
  *   unet_adam_step       optimizer.step() of torch.optim.Adam(model.parameters(),
  *                        lr, weight_decay) (train.py:49,331-335)
  *   unet_conv_* / unet_maxpool_* / unet_bn_*   single ops of the graph above
@@ -185,6 +188,22 @@ int unet_softmax_loss_forward(const float* logits, const void* labels, int label
 int unet_softmax_loss_backward(const float* logits, const void* labels, int label_dtype, int N, int K, int64_t HW,
                                const float* class_weights, int ignore_index, int kind, float alpha, float smooth,
                                const double* sums, const float* grad_scale, float* dlogits, hipStream_t stream);
+/* The same pair with per-pixel weights: pixel_weights is float [N][HW] on the
+ * device (any 4-B aligned base; 16-B accesses in the gradient kernel under the
+ * condition above when it is 16-B aligned too), or null.  A valid pixel then
+ * weighs class_weights[y] * pixel_weights[p] in ce_num, w_den and the CE part of
+ * the gradient; the valid / invalid counts, the Dice sums, the Dice gradient and
+ * the w_den == 0 rule are unchanged.  Weights must be finite and >= 0 (not
+ * checked).  Not allowed with kind 1.  With pixel_weights null both return the
+ * bits of the entries above. */
+int unet_softmax_loss_forward_pw(const float* logits, const void* labels, int label_dtype, int N, int K, int64_t HW,
+                                 const float* class_weights, const float* pixel_weights, int ignore_index, int kind,
+                                 float alpha, float smooth, double* sums, double* scratch, int64_t scratch_len,
+                                 float* loss_out, hipStream_t stream);
+int unet_softmax_loss_backward_pw(const float* logits, const void* labels, int label_dtype, int N, int K, int64_t HW,
+                                  const float* class_weights, const float* pixel_weights, int ignore_index, int kind,
+                                  float alpha, float smooth, const double* sums, const float* grad_scale,
+                                  float* dlogits, hipStream_t stream);
 /* cm: int64 [K][K] out, cm[t][p] = valid pixels of true class t whose first
  * maximum logit is channel p (lowest index on ties).  Exact integer counts. */
 int unet_confusion_matrix(const float* logits, const void* labels, int label_dtype, int N, int K, int64_t HW,
@@ -638,6 +657,60 @@ int unet_grow_instances(const int32_t* labels, int N, int H, int W,
                         const uint8_t* within /* nullable [N][H][W] */, int within_value /* -1: nonzero; 0..255: == */,
                         int32_t* out /* must not alias labels */,
                         void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
+/* ---- training targets for touching cells: the two nearest distinct instances,
+ * the border weight map and the interior / boundary targets (no reference
+ * counterpart) ----
+ * labels are int32 [N][H][W] of independent frames; the sites are the pixels with
+ * labels > 0 (any positive id; values <= 0 are unlabelled).
+ * unet_two_nearest_instances: for every pixel p the first site s1 minimises the
+ *   key (|p - s|^2, flat index of s) over all sites, compared lexicographically
+ *   (the key of unet_distance_transform); the second site s2 minimises the same
+ *   key over the sites whose label differs from labels[s1].
+ *     dist2 int32 [N][2][H][W]: |p - s1|^2 and |p - s2|^2, exact.
+ *     ids   int32 [N][2][H][W]: labels[s1] and labels[s2].
+ *   Where there is no such site, or it lies beyond max_dist2 (< 0: unlimited),
+ *   dist2 = UNET_DISTANCE_NONE and ids = 0.  A labelled pixel has dist2[0] = 0 and
+ *   its own id first.  Both squared distances are independent of the tie rule:
+ *   they are the two smallest entries of rint(distance_transform_edt(labels != i)
+ *   ** 2) over the ids i.  dist2 and ids are each optional, not both null.
+ *   H, W <= UNET_TWO_NEAREST_MAX_DIM (a row with two candidates and their labels
+ *   per column is staged in 12 W bytes of LDS).
+ * unet_border_weights: out[p] = base(p) + border(p), float [N][H][W].
+ *   base(p) = class_weights[classes[p]] when classes (uint8 [N][H][W]) and
+ *   class_weights (K floats on the device) are given (both or neither; a class >=
+ *   K gives 0), else 1.  border(p) = w0 exp(-(sqrt(d1) + sqrt(d2))^2 / (2 sigma^2))
+ *   on unlabelled pixels whose second instance exists within max_dist2, with d1,
+ *   d2 the squared distances above; 0 elsewhere (the weight map of the U-Net
+ *   paper).  The square roots and the exponential are taken in double and the sum
+ *   is rounded to float once.  w0 >= 0, sigma > 0.  Labelled pixels skip the scan;
+ *   d1 and d2 never go to memory.
+ * unet_boundary_targets: classes[p] = 0 where labels[p] <= 0 (background), 2 where
+ *   a labelled pixel has a neighbour inside the frame of another value (boundary;
+ *   connectivity 1: 4 neighbours, 2: 8), 1 at every other labelled pixel
+ *   (interior).  H, W <= UNET_DISTANCE_MAX_DIM, H W < 2^31.  No workspace.
+ * Integer arithmetic up to the weight, no atomics, one writer per output word: the
+ * outputs are bit-reproducible.  Plain launches on the caller's stream, no memset
+ * node: graph-capturable.  workspace: at least unet_two_nearest_workspace_bytes(N,
+ * H, W) bytes of device memory; it need not be initialised and holds nothing
+ * between calls.  Every bad argument (sizes, a null buffer, both outputs null, one
+ * of classes / class_weights alone, w0, sigma, connectivity, a short or null
+ * workspace) is an error with nothing launched. */
+#define UNET_TWO_NEAREST_MAX_DIM 4096
+/* host only; 0 (with unet_last_error) for N, H, W <= 0 or H, W > UNET_TWO_NEAREST_MAX_DIM */
+int64_t unet_two_nearest_workspace_bytes(int N, int H, int W);
+int unet_two_nearest_instances(const int32_t* labels, int N, int H, int W,
+                               int64_t max_dist2 /* < 0: unlimited */,
+                               int32_t* dist2 /* nullable [N][2][H][W] */, int32_t* ids /* nullable [N][2][H][W] */,
+                               void* workspace, int64_t workspace_bytes, hipStream_t stream);
+int unet_border_weights(const int32_t* labels, int N, int H, int W, float w0, float sigma,
+                        int64_t max_dist2 /* < 0: unlimited */,
+                        const uint8_t* classes /* nullable [N][H][W] */,
+                        const float* class_weights /* nullable, K floats on the device */, int K,
+                        float* out /* [N][H][W] */, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+int unet_boundary_targets(const int32_t* labels, int N, int H, int W,
+                          int connectivity /* 1: 4-neighbour, 2: 8-neighbour */,
+                          uint8_t* classes /* [N][H][W] */, hipStream_t stream);
 
 /* ---- matching of predicted instances to a ground truth (no reference
  * counterpart) ----
