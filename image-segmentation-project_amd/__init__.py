@@ -7,7 +7,9 @@ plus softmax losses and argmax metrics for mutually exclusive classes
 (``CrossEntropyLoss``, ``SoftmaxDiceLoss``, ``SoftmaxComboLoss``, ``confusion_matrix``)
 and tiled whole-frame inference on frames of any size (``predict``) with
 instance labelling of the predicted masks (``label_instances``), exact distance
-maps and growth of the instances (``distance_transform``, ``grow_instances``) and
+maps and growth of the instances (``distance_transform``, ``grow_instances``),
+growth along allowed pixels, watershed and splitting of touching cells
+(``geodesic_grow``, ``watershed``, ``split_instances``) and
 their scores against a ground truth (``match_instances``, ``instance_metrics``),
 and the training targets of that scheme from a ground-truth instance map
 (``boundary_targets``, ``border_weight_map``, ``nearest_two_instances``; per-pixel
@@ -30,6 +32,7 @@ from .dataset import CellAugmenter, CellSegmentationDataset, prepare_data, prepr
 from .predict import predict, tile_origins  # noqa: F401
 from .instances import instance_properties, label_instances  # noqa: F401
 from .distance import distance_transform, grow_instances  # noqa: F401
+from .geodesic import geodesic_grow, split_instances, watershed  # noqa: F401
 from .weights import border_weight_map, boundary_targets, nearest_two_instances  # noqa: F401
 from .match import InstanceMatch, instance_metrics, match_instances  # noqa: F401
 from . import ddp  # noqa: F401

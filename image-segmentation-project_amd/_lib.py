@@ -25,6 +25,7 @@ TILE_MAX = 1024  # UNET_TILE_MAX: largest tile of unet_tile_gather / unet_tile_b
 INSTANCE_STATS = 7  # UNET_INSTANCE_STATS: area, sum_y, sum_x, y0, x0, y1, x1
 DISTANCE_NONE = 2147483647  # UNET_DISTANCE_NONE: dist2 of a frame without a site
 DISTANCE_MAX_DIM = 32768  # UNET_DISTANCE_MAX_DIM: largest H and W of the distance transform
+GEODESIC_MAX_HW = 1 << 28  # UNET_GEODESIC_MAX_HW: largest H * W of geodesic growth / watershed (int32 chamfer costs)
 TWO_NEAREST_MAX_DIM = 4096  # UNET_TWO_NEAREST_MAX_DIM: largest H and W of the two-nearest transform / border weights
 MATCH_COLS = 4  # UNET_MATCH_COLS: area, partner, intersection, partner_area
 MATCH_STATUS = 5  # UNET_MATCH_STATUS: n_gt, n_pred, n_pairs, dropped, out_of_range
@@ -186,6 +187,11 @@ SIGNATURES = {
     "unet_distance_transform": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p] * 3 + [c_int64, c_void_p]),
     "unet_grow_instances": (c_int, [c_void_p] + [c_int] * 3 + [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64,
                                                                 c_void_p]),
+    "unet_geodesic_workspace_bytes": (c_int64, [c_int] * 3),
+    "unet_geodesic_grow": (c_int, [c_void_p] + [c_int] * 4 + [c_int64, c_void_p, c_int] + [c_void_p] * 3
+                           + [c_int64, c_void_p]),
+    "unet_watershed": (c_int, [c_void_p] * 2 + [c_int] * 4 + [c_void_p, c_int] + [c_void_p] * 2 + [c_int64, c_void_p]),
+    "unet_geodesic_last_counts": (c_int, [c_void_p] * 3),
     "unet_two_nearest_workspace_bytes": (c_int64, [c_int] * 3),
     "unet_two_nearest_instances": (c_int, [c_void_p] + [c_int] * 3 + [c_int64] + [c_void_p] * 3 + [c_int64, c_void_p]),
     "unet_border_weights": (c_int, [c_void_p] + [c_int] * 3 + [c_float, c_float, c_int64, c_void_p, c_void_p, c_int,

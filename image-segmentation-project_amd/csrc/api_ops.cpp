@@ -820,6 +820,76 @@ int unet_grow_instances(const int32_t* labels, int N, int H, int W, int64_t max_
   return 0;
 }
 
+// ---- geodesic growth and watershed by levels (geodesic.hip) ----
+static_assert(kGeoMaxDim == UNET_DISTANCE_MAX_DIM && kGeoMaxHW == UNET_GEODESIC_MAX_HW, "size limits of the header");
+
+static bool geodesic_shape_ok(const char* fn, int N, int H, int W) {
+  if (N > 0 && H > 0 && W > 0 && H <= kGeoMaxDim && W <= kGeoMaxDim && (int64_t)H * W <= kGeoMaxHW) return true;
+  return errf("%s: N = %d, H = %d, W = %d must be positive with H, W <= %d and H * W <= 2^28", fn, N, H, W,
+              kGeoMaxDim);
+}
+
+// the arguments the two entries share, then "the stream is not capturing": these calls wait for the stream
+static bool geodesic_args_ok(const char* fn, int N, int H, int W, int metric, int within_value, const void* workspace,
+                             int64_t workspace_bytes, hipStream_t stream) {
+  if (!geodesic_shape_ok(fn, N, H, W)) return false;
+  if (metric != 0 && metric != 1) return errf("%s: metric = %d must be 0 (cityblock) or 1 (chamfer)", fn, metric);
+  if (within_value < -1 || within_value > 255)
+    return errf("%s: within_value = %d must be -1 or 0..255", fn, within_value);
+  if (!workspace_ok(fn, "unet_geodesic_workspace_bytes", workspace, workspace_bytes,
+                    geodesic_workspace_bytes(N, H, W)))
+    return false;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  const hipError_t e = hipStreamIsCapturing(stream, &cs);
+  if (e != hipSuccess || cs != hipStreamCaptureStatusNone) {
+    (void)hipGetLastError();
+    return errf("%s: the stream is capturing (%s); the call reads its convergence back on the host and cannot be "
+                "captured into a graph", fn, e != hipSuccess ? hipGetErrorString(e) : "active");
+  }
+  return true;
+}
+
+int64_t unet_geodesic_workspace_bytes(int N, int H, int W) {
+  if (!geodesic_shape_ok("unet_geodesic_workspace_bytes", N, H, W)) return 0;
+  return geodesic_workspace_bytes(N, H, W);
+}
+
+int unet_geodesic_grow(const int32_t* labels, int N, int H, int W, int metric, int64_t max_cost,
+                       const uint8_t* within, int within_value, int32_t* out, int32_t* cost, void* workspace,
+                       int64_t workspace_bytes, hipStream_t stream) {
+  const char* fn = "unet_geodesic_grow";
+  if (!labels || !out) { set_err("unet_geodesic_grow: labels / out is null"); return 1; }
+  if (out == labels || cost == labels || (cost && cost == out)) {
+    set_err("unet_geodesic_grow: out / cost must not alias labels or each other");
+    return 1;
+  }
+  if (!geodesic_args_ok(fn, N, H, W, metric, within_value, workspace, workspace_bytes, stream)) return 1;
+  const GeoArgs a{labels, N, H, W, metric, max_cost, within, within_value, nullptr, out, cost, workspace,
+                  workspace_bytes};
+  CK(launch_geodesic(a, stream));
+  return 0;
+}
+
+int unet_watershed(const uint8_t* relief, const int32_t* markers, int N, int H, int W, int metric,
+                   const uint8_t* mask, int mask_value, int32_t* out, void* workspace, int64_t workspace_bytes,
+                   hipStream_t stream) {
+  const char* fn = "unet_watershed";
+  if (!relief || !markers || !out) { set_err("unet_watershed: relief / markers / out is null"); return 1; }
+  if (out == markers) { set_err("unet_watershed: out must not alias markers"); return 1; }
+  if (!geodesic_args_ok(fn, N, H, W, metric, mask_value, workspace, workspace_bytes, stream)) return 1;
+  const GeoArgs a{markers, N, H, W, metric, -1, mask, mask_value, relief, out, nullptr, workspace, workspace_bytes};
+  CK(launch_geodesic(a, stream));
+  return 0;
+}
+
+int unet_geodesic_last_counts(int* passes, int* changing_passes, int* readbacks) {
+  const GeoCounts c = geodesic_last_counts();
+  if (passes) *passes = c.passes;
+  if (changing_passes) *changing_passes = c.changing;
+  if (readbacks) *readbacks = c.readbacks;
+  return 0;
+}
+
 // ---- two nearest distinct instances, border weights, boundary targets (weights.hip) ----
 static_assert(kTwoMaxDim == UNET_TWO_NEAREST_MAX_DIM, "size limit of the header");
 

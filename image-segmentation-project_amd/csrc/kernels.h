@@ -551,6 +551,32 @@ int64_t distance_workspace_bytes(int N, int H, int W);
 // hipErrorInvalidValue (nothing launched) on a null buffer, a bad argument or a short workspace
 hipError_t launch_distance(const DistArgs& a, hipStream_t st);
 
+// geodesic growth of a label map and marker watershed by levels (geodesic.hip)
+constexpr int kGeoTH = 32, kGeoTW = 64;            // tile of a relaxation pass (one block, LDS with a 1-pixel halo)
+constexpr int kGeoBatch = 4;                       // passes enqueued between two readbacks of the "changed" words
+constexpr int kGeoMaxDim = kDistMaxDim;            // H, W <= this
+constexpr int64_t kGeoMaxHW = (int64_t)1 << 28;    // H W <= this: a chamfer cost (<= 4 H W) fits an int32
+struct GeoArgs {
+  const int* labels;     // [N][H][W]; labels != 0 are the sources (the markers of the watershed)
+  int N, H, W;
+  int metric;            // 0: cityblock (4 neighbours, 1); 1: chamfer (8 neighbours, 3 / 4)
+  int64_t max_cost;      // < 0: unlimited
+  const uint8_t* within; // [N][H][W] or null (the mask of the watershed)
+  int within_value;      // -1: nonzero; 0..255: == value
+  const uint8_t* relief; // [N][H][W]: watershed by levels; null: one growth
+  int* out;              // [N][H][W], must not alias labels
+  int* cost;             // [N][H][W] or null; null with relief
+  void* workspace; int64_t workspace_bytes;
+};
+struct GeoCounts { int passes, changing, readbacks; };  // of this thread's last call: passes launched, passes
+                                                        // that changed a tile border, host readbacks
+// 0 for N, H, W <= 0, H or W > 32768 or H W > 2^28
+int64_t geodesic_workspace_bytes(int N, int H, int W);
+// hipErrorInvalidValue (nothing launched) on a null buffer, a bad argument or a short workspace.
+// Synchronises with the stream; the caller refuses a capturing stream.
+hipError_t launch_geodesic(const GeoArgs& a, hipStream_t st);
+GeoCounts geodesic_last_counts();
+
 // two nearest distinct instances, border weight map, boundary targets (weights.hip)
 constexpr int kTwoMaxDim = 4096;  // H, W <= this: a row's two candidates with their labels are 12 W bytes of LDS
 struct TwoArgs {

@@ -77,7 +77,7 @@ def grow_instances(labels, max_distance=None, within=None, within_value=None):
     pixel is allowed where it is nonzero, or, with ``within_value=c``, where it
     equals ``c`` (``within=predict(..., output="labels"), within_value=2`` for a
     boundary class).  Labelled pixels are copied.  "Nearest" is measured over the
-    whole frame, not along allowed pixels.
+    whole frame, not along allowed pixels (``geodesic_grow`` measures along them).
 
     Returns int32 labels of the same shape; the set of ids is unchanged (as
     ``skimage.segmentation.expand_labels``).  The input is not modified.

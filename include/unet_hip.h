@@ -19,6 +19,8 @@
  *                        definitions; the reference's host-side post-processing is not ported)
  *   unet_distance_transform / unet_grow_instances   exact Euclidean distance and nearest-site
  *                        transform of masks and label maps, nearest-label growth of instances
+ *   unet_geodesic_grow / unet_watershed   growth of a label map along allowed pixels (shortest
+ *                        paths) and marker watershed by levels; these synchronise with the host
  *   unet_match_instances IoU tables of predicted instances against a ground truth label map
  *   unet_two_nearest_instances / unet_border_weights / unet_boundary_targets   training targets
  *                        for touching cells from a ground-truth instance map; unet_softmax_loss_*_pw
@@ -657,6 +659,54 @@ int unet_grow_instances(const int32_t* labels, int N, int H, int W,
                         const uint8_t* within /* nullable [N][H][W] */, int within_value /* -1: nonzero; 0..255: == */,
                         int32_t* out /* must not alias labels */,
                         void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
+/* ---- geodesic growth of a label map and marker watershed by levels (no
+ * reference counterpart) ----
+ * Frames [N][H][W] are independent.  H, W <= UNET_DISTANCE_MAX_DIM and H W <=
+ * UNET_GEODESIC_MAX_HW = 2^28, so that no cost overflows an int32.
+ * metric 0 (cityblock): 4 neighbours, a step costs 1.  metric 1 (chamfer): 8
+ *   neighbours, an axial step costs 3 and a diagonal step 4; a diagonal step is
+ *   allowed whatever the two axial neighbours are.
+ * unet_geodesic_grow: labels != 0 are labelled (positive ids; a negative value is a
+ *   caller error that is copied like an id, ids are never used as indices).  A
+ *   pixel is free when it is unlabelled and allowed (within null: every pixel;
+ *   else within[p] nonzero for within_value = -1, within[p] == within_value for
+ *   0..255).  A path runs from a free pixel p to a labelled pixel s by steps of the
+ *   metric through free pixels only; d(p) is the least cost of such a path with
+ *   d(p) <= max_cost (max_cost < 0: unlimited), and out[p] is the smallest id among
+ *   the labelled pixels that reach p at cost d(p).  Labelled pixels are copied,
+ *   pixels without a path stay 0.  cost (optional): 0 at labelled pixels, d(p) at
+ *   reached ones, -1 elsewhere.  Equals Dijkstra from all labelled pixels at once
+ *   with the key (cost, id), relaxing into free pixels only.
+ * unet_watershed: flooding by levels.  For every value h of relief (uint8) that
+ *   occurs under the mask, ascending: markers <- unet_geodesic_grow(markers, within
+ *   = mask and relief <= h), unlimited; the predicate is evaluated in the kernel.
+ *   Marker pixels keep their id whatever relief and mask say; unreached pixels
+ *   stay 0.  mask / mask_value as within / within_value.
+ * Both SYNCHRONISE with the host: relaxation passes run until one changes
+ *   nothing, which the host learns by reading 4-byte words back on the caller's
+ *   stream (the watershed also reads a 256-bin histogram once).  They cannot be
+ *   captured into a graph: on a capturing stream they fail with an error and
+ *   enqueue nothing.  unet_geodesic_last_counts: passes launched, passes that
+ *   changed a tile border and host readbacks of the calling thread's last call.
+ * Integer arithmetic, a unique fixed point: the outputs are bit-reproducible.
+ * Inputs are never modified; out must not alias labels / markers.  workspace: at
+ * least unet_geodesic_workspace_bytes(N, H, W) bytes of device memory (8 bytes
+ * per pixel and a little); it need not be initialised and holds nothing between
+ * calls.  Every bad argument is an error with nothing launched. */
+#define UNET_GEODESIC_MAX_HW 268435456
+/* host only; 0 (with unet_last_error) for N, H, W <= 0, H or W > 32768 or H W > 2^28 */
+int64_t unet_geodesic_workspace_bytes(int N, int H, int W);
+int unet_geodesic_grow(const int32_t* labels, int N, int H, int W, int metric /* 0 cityblock, 1 chamfer */,
+                       int64_t max_cost /* < 0: unlimited */,
+                       const uint8_t* within /* nullable [N][H][W] */, int within_value /* -1: nonzero; 0..255: == */,
+                       int32_t* out /* must not alias labels */, int32_t* cost /* nullable */,
+                       void* workspace, int64_t workspace_bytes, hipStream_t stream);
+int unet_watershed(const uint8_t* relief, const int32_t* markers, int N, int H, int W, int metric,
+                   const uint8_t* mask /* nullable [N][H][W] */, int mask_value /* -1: nonzero; 0..255: == */,
+                   int32_t* out /* must not alias markers */,
+                   void* workspace, int64_t workspace_bytes, hipStream_t stream);
+int unet_geodesic_last_counts(int* passes, int* changing_passes, int* readbacks);
 
 /* ---- training targets for touching cells: the two nearest distinct instances,
  * the border weight map and the interior / boundary targets (no reference
