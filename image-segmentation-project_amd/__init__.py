@@ -11,6 +11,9 @@ maps and growth of the instances (``distance_transform``, ``grow_instances``),
 growth along allowed pixels, watershed and splitting of touching cells
 (``geodesic_grow``, ``watershed``, ``split_instances``) and
 their scores against a ground truth (``match_instances``, ``instance_metrics``),
+per-instance shape, contact and intensity tables of any label map
+(``measure_instances``, ``region_properties``) with filtering and renumbering on
+the device (``select_instances``),
 and the training targets of that scheme from a ground-truth instance map
 (``boundary_targets``, ``border_weight_map``, ``nearest_two_instances``; per-pixel
 weights in ``CrossEntropyLoss`` / ``SoftmaxComboLoss``),
@@ -35,6 +38,8 @@ from .distance import distance_transform, grow_instances  # noqa: F401
 from .geodesic import geodesic_grow, split_instances, watershed  # noqa: F401
 from .weights import border_weight_map, boundary_targets, nearest_two_instances  # noqa: F401
 from .match import InstanceMatch, instance_metrics, match_instances  # noqa: F401
+from .measure import (MEASURE_COLUMNS, InstanceMeasure, measure_instances, region_properties,  # noqa: F401
+                      select_instances)
 from . import ddp  # noqa: F401
 from . import optim  # noqa: F401
 from .optim import Adam  # noqa: F401

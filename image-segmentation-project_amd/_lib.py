@@ -29,6 +29,9 @@ GEODESIC_MAX_HW = 1 << 28  # UNET_GEODESIC_MAX_HW: largest H * W of geodesic gro
 TWO_NEAREST_MAX_DIM = 4096  # UNET_TWO_NEAREST_MAX_DIM: largest H and W of the two-nearest transform / border weights
 MATCH_COLS = 4  # UNET_MATCH_COLS: area, partner, intersection, partner_area
 MATCH_STATUS = 5  # UNET_MATCH_STATUS: n_gt, n_pred, n_pairs, dropped, out_of_range
+MEASURE_COLS = 13  # UNET_MEASURE_COLS: area, sums, box, second-order sums, edges, frame_edges, contact_edges
+MEASURE_STATUS = 3  # UNET_MEASURE_STATUS: n_present, max_id, out_of_range
+MEASURE_ICOLS = 4  # UNET_MEASURE_ICOLS: sum, sum_sq, min, max
 
 _lib = None
 
@@ -199,6 +202,9 @@ SIGNATURES = {
     "unet_boundary_targets": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p, c_void_p]),
     "unet_match_workspace_bytes": (c_int64, [c_int] * 4),
     "unet_match_instances": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p] * 5 + [c_int64, c_void_p]),
+    "unet_measure_workspace_bytes": (c_int64, [c_int] * 5),
+    "unet_measure_instances": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p] * 4 + [c_int64, c_void_p]),
+    "unet_select_instances": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 4),
     "unet_maxpool_fwd": (c_int,[c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
     "unet_maxpool_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 4 + [c_void_p]),
 }

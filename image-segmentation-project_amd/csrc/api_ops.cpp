@@ -987,6 +987,73 @@ int unet_match_instances(const int32_t* gt, const int32_t* pred, int N, int H, i
   return 0;
 }
 
+// ---- measuring and selecting instances (measure.hip) ----
+static_assert(kMeasureMaxDim == UNET_DISTANCE_MAX_DIM && kMeasureMaxHW == UNET_GEODESIC_MAX_HW,
+              "size limits of the header");
+
+static bool measure_shape_ok(const char* fn, int N, int H, int W) {
+  if (N > 0 && H > 0 && W > 0 && H <= kMeasureMaxDim && W <= kMeasureMaxDim && (int64_t)H * W <= kMeasureMaxHW)
+    return true;
+  return errf("%s: N = %d, H = %d, W = %d must be positive with H, W <= %d and H * W <= 2^28", fn, N, H, W,
+              kMeasureMaxDim);
+}
+
+static bool measure_caps_ok(const char* fn, int max_instances, int channels) {
+  if (max_instances >= 1 && max_instances <= kMeasureMaxId && channels >= 0 && channels <= kMeasureMaxChannels)
+    return true;
+  return errf("%s: max_instances = %d must be in 1..%d and channels = %d in 0..%d", fn, max_instances, kMeasureMaxId,
+              channels, kMeasureMaxChannels);
+}
+
+int64_t unet_measure_workspace_bytes(int N, int H, int W, int max_instances, int channels) {
+  const char* fn = "unet_measure_workspace_bytes";
+  if (!measure_shape_ok(fn, N, H, W) || !measure_caps_ok(fn, max_instances, channels)) return 0;
+  return measure_workspace_bytes(N, H, W, max_instances, channels);
+}
+
+int unet_measure_instances(const int32_t* labels, const void* image, int image_dtype, int channels, int N, int H,
+                           int W, int max_instances, int64_t* table, int64_t* status, void* intensity,
+                           void* workspace, int64_t workspace_bytes, hipStream_t stream) {
+  const char* fn = "unet_measure_instances";
+  if (!labels || !table || !status) { set_err("unet_measure_instances: labels / table / status is null"); return 1; }
+  if ((image != nullptr) != (intensity != nullptr)) {
+    set_err("unet_measure_instances: image and intensity go together, one of them is null");
+    return 1;
+  }
+  if (!measure_shape_ok(fn, N, H, W) || !measure_caps_ok(fn, max_instances, channels)) return 1;
+  if (image ? (channels < 1 || image_dtype < 0 || image_dtype > 2) : (channels != 0 || image_dtype != 0)) {
+    errf("%s: with an image channels = %d must be in 1..%d and image_dtype = %d 0 (uint8), 1 (uint16) or 2 "
+         "(float32); without one both must be 0", fn, channels, kMeasureMaxChannels, image_dtype);
+    return 1;
+  }
+  if (!workspace_ok(fn, "unet_measure_workspace_bytes", workspace, workspace_bytes,
+                    measure_workspace_bytes(N, H, W, max_instances, channels)))
+    return 1;
+  const MeasureArgs a{labels, image, image_dtype, channels, N, H, W, max_instances,
+                      reinterpret_cast<long long*>(table), reinterpret_cast<long long*>(status), intensity, workspace,
+                      workspace_bytes};
+  CK(launch_measure_instances(a, stream));
+  return 0;
+}
+
+int unet_select_instances(const int32_t* labels, const uint8_t* keep, int N, int H, int W, int M,
+                          int32_t* labels_out, int32_t* counts, int32_t* new_ids, hipStream_t stream) {
+  const char* fn = "unet_select_instances";
+  if (!labels || !keep || !labels_out || !counts || !new_ids) {
+    set_err("unet_select_instances: labels / keep / labels_out / counts / new_ids is null");
+    return 1;
+  }
+  if (labels_out == labels) { set_err("unet_select_instances: labels_out must not alias labels"); return 1; }
+  if (!measure_shape_ok(fn, N, H, W)) return 1;
+  if (M < 1 || M > kMeasureMaxId) {
+    errf("%s: M = %d must be in 1..%d", fn, M, kMeasureMaxId);
+    return 1;
+  }
+  const SelectArgs a{labels, keep, N, H, W, M, labels_out, counts, new_ids};
+  CK(launch_select_instances(a, stream));
+  return 0;
+}
+
 int unet_maxpool_fwd(const void* x, int ldx, void* y, uint8_t* idx, int N, int H, int W, int C,
                      hipStream_t stream) {
   MaxPoolArgs m = {};

@@ -621,6 +621,36 @@ int64_t match_workspace_bytes(int N, int max_gt, int max_pred, int max_pairs);
 // hipErrorInvalidValue (nothing launched) on a null buffer, a bad argument or a short workspace
 hipError_t launch_match_instances(const MatchArgs& a, hipStream_t st);
 
+// measuring the instances of a label map and selecting among them (measure.hip)
+constexpr int kMeasureLdsSlots = 64;               // ids of the LDS table of a 32 x 64 tile
+constexpr int kMeasureMaxId = 65535;               // max_instances and the M of select_instances
+constexpr int kMeasureMaxDim = 32768;              // H, W <= this and
+constexpr int64_t kMeasureMaxHW = (int64_t)1 << 28; // H W <= this: every 64-bit sum stays exact
+constexpr int kMeasureMaxChannels = 4;
+struct MeasureArgs {
+  const int* labels;      // [N][H][W]
+  const void* image;      // [N][channels][H][W] uint8 (image_dtype 0), uint16 (1) or float (2); or null
+  int image_dtype, channels;
+  int N, H, W, max_inst;
+  long long* table;       // [N][max_inst][UNET_MEASURE_COLS]
+  long long* status;      // [N][UNET_MEASURE_STATUS]
+  void* intensity;        // [N][max_inst][channels][UNET_MEASURE_ICOLS] int64, double for a float image; null with image
+  void* workspace; int64_t workspace_bytes;
+};
+// 0 for N, H, W <= 0, H or W > 32768, H W > 2^28, max_inst outside 1..65535 or channels outside 0..4
+int64_t measure_workspace_bytes(int N, int H, int W, int max_inst, int channels);
+// hipErrorInvalidValue (nothing launched) on a null buffer, a bad argument or a short workspace
+hipError_t launch_measure_instances(const MeasureArgs& a, hipStream_t st);
+struct SelectArgs {
+  const int* labels;      // [N][H][W]
+  const uint8_t* keep;    // [N][M], nonzero = keep id (index + 1)
+  int N, H, W, M;
+  int* labels_out;        // [N][H][W], must not alias labels
+  int* counts;            // [N]
+  int* new_ids;           // [N][M]
+};
+hipError_t launch_select_instances(const SelectArgs& a, hipStream_t st);
+
 // attention decoder (attention.hip; advanced_models.py:7-61)
 struct AttGateArgs {
   const bf16_t* s; int lds;            // relu(BN_g + BN_x), F_int channels

@@ -22,6 +22,8 @@
  *   unet_geodesic_grow / unet_watershed   growth of a label map along allowed pixels (shortest
  *                        paths) and marker watershed by levels; these synchronise with the host
  *   unet_match_instances IoU tables of predicted instances against a ground truth label map
+ *   unet_measure_instances / unet_select_instances   per-instance shape, contact and intensity
+ *                        tables of a label map; dropping and renumbering of instances
  *   unet_two_nearest_instances / unet_border_weights / unet_boundary_targets   training targets
  *                        for touching cells from a ground-truth instance map; unet_softmax_loss_*_pw
  *                        take the weight map as per-pixel weights of the cross-entropy
@@ -806,6 +808,63 @@ int unet_match_instances(const int32_t* gt, const int32_t* pred, int N, int H, i
                          int64_t* status,      /* [N][5] */
                          int64_t* pairs,       /* nullable [N][max_pairs][3]: gt, pred, intersection */
                          void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
+/* ---- measuring the instances of a label map, selecting among them (no reference
+ * counterpart) ----
+ * labels is an int32 label map [N][H][W] of independent frames, H, W <=
+ * UNET_DISTANCE_MAX_DIM and H W <= UNET_GEODESIC_MAX_HW (2^28): 0 is background,
+ * the instances carry ids 1..max_instances (in 1..65535; the ids need not be
+ * compact).  A pixel with a value below 0 or above max_instances belongs to no
+ * instance; as a neighbour it is another nonzero value.  Per frame:
+ *   table int64 [N][max_instances][UNET_MEASURE_COLS], row id - 1, over the pixels
+ *     (y, x) of value id: area; sum_y, sum_x; y0, x0, y1, x1 (the half-open box;
+ *     these seven as the stats of unet_label_instances); sum_yy, sum_xx, sum_xy
+ *     (sums of y y, x x, y x); edges (the pixel sides up, down, left, right whose
+ *     other side lies outside the frame or holds a different value: the
+ *     crack-length perimeter); frame_edges (those on the frame's border);
+ *     contact_edges (those whose other side is inside the frame and nonzero).  The
+ *     row of an id that does not occur is all zero.
+ *   status int64 [N][UNET_MEASURE_STATUS]: n_present (the ids in 1..max_instances
+ *     that occur), max_id (the largest of them, 0 if none), out_of_range (the
+ *     pixels with a value outside 0..max_instances).
+ *   intensity (with image; both null otherwise) [N][max_instances][channels]
+ *     [UNET_MEASURE_ICOLS]: sum, sum_sq, min, max of the image over the pixels of
+ *     the id; image is [N][channels][H][W], channels in 1..4, of image_dtype 0
+ *     (uint8), 1 (uint16) or 2 (float32, finite values; not checked).  Integer
+ *     images give an int64 table of exact sums, a float image a double table with
+ *     exact min and max.  Rows of absent ids are zero.  Without an image channels
+ *     and image_dtype must be 0.
+ * Everything but sum and sum_sq of a float image is a sum, minimum or maximum of
+ * integers through integer atomics and bit-reproducible; those two are fp64
+ * atomic sums and depend on the order of arrival in their last bits.  labels and
+ * image are only read.
+ * workspace: at least unet_measure_workspace_bytes(...) bytes of device memory
+ * (the accumulators: 8 (13 + 4 channels) bytes per row of the table); it need not
+ * be initialised and holds nothing between calls.
+ *
+ * unet_select_instances: keep is uint8 [N][M], M in 1..65535; entry id - 1 nonzero
+ * = id survives.  new_ids int32 [N][M]: the 1-based rank of a kept id among the
+ * kept ids in ascending order, 0 for a dropped id; counts int32 [N]: the number of
+ * kept ids; labels_out int32 [N][H][W] (not labels itself): new_ids[id - 1] for
+ * the values 1..M of labels, 0 for every other value.
+ * Every bad argument (a null buffer, image without intensity or the reverse, sizes,
+ * caps, channels, image_dtype, a short or null workspace) is an error with nothing
+ * launched. */
+#define UNET_MEASURE_COLS 13   /* area, sum_y, sum_x, y0, x0, y1, x1, sum_yy, sum_xx, sum_xy, edges, frame_edges, contact_edges */
+#define UNET_MEASURE_STATUS 3  /* n_present, max_id, out_of_range */
+#define UNET_MEASURE_ICOLS 4   /* sum, sum_sq, min, max */
+/* host only; 0 (with unet_last_error) for a bad argument */
+int64_t unet_measure_workspace_bytes(int N, int H, int W, int max_instances, int channels);
+int unet_measure_instances(const int32_t* labels, const void* image /* nullable */,
+                           int image_dtype /* 0: uint8, 1: uint16, 2: float32 */, int channels,
+                           int N, int H, int W, int max_instances,
+                           int64_t* table,   /* [N][max_instances][13] row id - 1 */
+                           int64_t* status,  /* [N][3] */
+                           void* intensity,  /* nullable with image: [N][max_instances][channels][4] int64 / double */
+                           void* workspace, int64_t workspace_bytes, hipStream_t stream);
+int unet_select_instances(const int32_t* labels, const uint8_t* keep /* [N][M] */, int N, int H, int W, int M,
+                          int32_t* labels_out /* [N][H][W] */, int32_t* counts /* [N] */,
+                          int32_t* new_ids /* [N][M] */, hipStream_t stream);
 
 #ifdef __cplusplus
 }
