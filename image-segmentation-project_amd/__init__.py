@@ -14,6 +14,8 @@ their scores against a ground truth (``match_instances``, ``instance_metrics``),
 per-instance shape, contact and intensity tables of any label map
 (``measure_instances``, ``region_properties``) with filtering and renumbering on
 the device (``select_instances``),
+linking of the instances of consecutive frames into tracks or 3-D objects
+(``link_instances``, ``track_properties``),
 and the training targets of that scheme from a ground-truth instance map
 (``boundary_targets``, ``border_weight_map``, ``nearest_two_instances``; per-pixel
 weights in ``CrossEntropyLoss`` / ``SoftmaxComboLoss``),
@@ -40,6 +42,7 @@ from .weights import border_weight_map, boundary_targets, nearest_two_instances 
 from .match import InstanceMatch, instance_metrics, match_instances  # noqa: F401
 from .measure import (MEASURE_COLUMNS, InstanceMeasure, measure_instances, region_properties,  # noqa: F401
                       select_instances)
+from .track import TRACK_COLUMNS, TRACK_STATUS, InstanceLinks, link_instances, track_properties  # noqa: F401
 from . import ddp  # noqa: F401
 from . import optim  # noqa: F401
 from .optim import Adam  # noqa: F401

@@ -32,6 +32,10 @@ MATCH_STATUS = 5  # UNET_MATCH_STATUS: n_gt, n_pred, n_pairs, dropped, out_of_ra
 MEASURE_COLS = 13  # UNET_MEASURE_COLS: area, sums, box, second-order sums, edges, frame_edges, contact_edges
 MEASURE_STATUS = 3  # UNET_MEASURE_STATUS: n_present, max_id, out_of_range
 MEASURE_ICOLS = 4  # UNET_MEASURE_ICOLS: sum, sum_sq, min, max
+LINK_COLS = 4  # UNET_LINK_COLS: first, last, parent, volume
+LINK_STATUS = 4  # UNET_LINK_STATUS: n_tracks, n_links, dropped, out_of_range
+LINK_BLOCK = 1024  # UNET_LINK_BLOCK: ids per chunk of the resolve pass
+LINK_LDS_IDS = 8191  # UNET_LINK_LDS_IDS: largest max_instances whose LUT row the relabel pass keeps in LDS
 
 _lib = None
 
@@ -205,6 +209,8 @@ SIGNATURES = {
     "unet_measure_workspace_bytes": (c_int64, [c_int] * 5),
     "unet_measure_instances": (c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p] * 4 + [c_int64, c_void_p]),
     "unet_select_instances": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p] * 4),
+    "unet_link_workspace_bytes": (c_int64, [c_int] * 4),
+    "unet_link_instances": (c_int, [c_void_p] + [c_int] * 9 + [c_void_p] * 4 + [c_int64, c_void_p]),
     "unet_maxpool_fwd": (c_int,[c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
     "unet_maxpool_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 4 + [c_void_p]),
 }

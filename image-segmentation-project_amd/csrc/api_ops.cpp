@@ -1054,6 +1054,51 @@ int unet_select_instances(const int32_t* labels, const uint8_t* keep, int N, int
   return 0;
 }
 
+// ---- linking instances across frames (track.hip) ----
+static bool link_caps_ok(const char* fn, int B, int T, int max_instances, int max_pairs) {
+  if (B > 0 && T > 0 && T <= kLinkMaxFrames && (int64_t)B * T <= INT32_MAX && max_instances >= 1 &&
+      max_instances <= kMatchMaxId && max_pairs >= 1 && max_pairs <= kMatchMaxPairs)
+    return true;
+  return errf("%s: B = %d must be positive, T = %d in 1..%d with B * T < 2^31, max_instances = %d in 1..%d, "
+              "max_pairs = %d in 1..%d", fn, B, T, kLinkMaxFrames, max_instances, kMatchMaxId, max_pairs,
+              kMatchMaxPairs);
+}
+
+int64_t unet_link_workspace_bytes(int B, int T, int max_instances, int max_pairs) {
+  if (!link_caps_ok("unet_link_workspace_bytes", B, T, max_instances, max_pairs)) return 0;
+  return link_workspace_bytes(B, T, max_instances, max_pairs);
+}
+
+int unet_link_instances(const int32_t* labels, int B, int T, int H, int W, int max_instances, int max_pairs,
+                        int max_tracks, int iou_num, int iou_den, int32_t* tracks_out, int64_t* table,
+                        int64_t* status, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
+  const char* fn = "unet_link_instances";
+  if (!labels || !tracks_out || !table || !status) {
+    set_err("unet_link_instances: labels / tracks_out / table / status is null");
+    return 1;
+  }
+  if (tracks_out == labels) { set_err("unet_link_instances: tracks_out must not alias labels"); return 1; }
+  if (!measure_shape_ok(fn, B, H, W) || !link_caps_ok(fn, B, T, max_instances, max_pairs)) return 1;
+  if (max_tracks < 1) { errf("%s: max_tracks = %d must be >= 1", fn, max_tracks); return 1; }
+  if (iou_den < 1 || iou_num < 0 || iou_num >= iou_den) {
+    errf("%s: the threshold iou_num / iou_den = %d / %d must satisfy 0 <= iou_num < iou_den", fn, iou_num, iou_den);
+    return 1;
+  }
+  const int64_t per_frame = (int64_t)H * W < max_instances ? (int64_t)H * W : max_instances;
+  if ((int64_t)T * per_frame > INT32_MAX) {
+    errf("%s: T * min(max_instances, H * W) = %lld track ids do not fit int32", fn, (long long)(T * per_frame));
+    return 1;
+  }
+  if (!workspace_ok(fn, "unet_link_workspace_bytes", workspace, workspace_bytes,
+                    link_workspace_bytes(B, T, max_instances, max_pairs)))
+    return 1;
+  const LinkArgs a{labels, B, T, H, W, max_instances, max_pairs, max_tracks, iou_num, iou_den, tracks_out,
+                   reinterpret_cast<long long*>(table), reinterpret_cast<long long*>(status), workspace,
+                   workspace_bytes};
+  CK(launch_link_instances(a, stream));
+  return 0;
+}
+
 int unet_maxpool_fwd(const void* x, int ldx, void* y, uint8_t* idx, int N, int H, int W, int C,
                      hipStream_t stream) {
   MaxPoolArgs m = {};

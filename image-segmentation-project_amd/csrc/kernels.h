@@ -651,6 +651,25 @@ struct SelectArgs {
 };
 hipError_t launch_select_instances(const SelectArgs& a, hipStream_t st);
 
+// linking the instances of consecutive frames into tracks (track.hip), on the tables of match.hip
+constexpr int kLinkBlock = 1024;       // threads of the resolve block = ids per chunk of its scan
+constexpr int kLinkLdsIds = 8191;      // relabel: max_inst <= this stages a frame's LUT row (32 KiB) in LDS
+constexpr int kLinkMaxFrames = 65535;  // T
+struct LinkArgs {
+  const int* labels;      // [B][T][H][W]
+  int B, T, H, W;
+  int max_inst, max_pairs, max_tracks;
+  int iou_num, iou_den;   // a link needs IoU > iou_num / iou_den; 0 <= iou_num < iou_den
+  int* tracks;            // [B][T][H][W], must not alias labels
+  long long* table;       // [B][max_tracks][UNET_LINK_COLS]
+  long long* status;      // [B][UNET_LINK_STATUS]
+  void* workspace; int64_t workspace_bytes;
+};
+// 0 for B, T <= 0, T > 65535, max_inst outside 1..65535 or max_pairs outside 1..2^24
+int64_t link_workspace_bytes(int B, int T, int max_inst, int max_pairs);
+// hipErrorInvalidValue (nothing launched) on a null buffer, a bad argument or a short workspace
+hipError_t launch_link_instances(const LinkArgs& a, hipStream_t st);
+
 // attention decoder (attention.hip; advanced_models.py:7-61)
 struct AttGateArgs {
   const bf16_t* s; int lds;            // relu(BN_g + BN_x), F_int channels

@@ -24,6 +24,8 @@
  *   unet_match_instances IoU tables of predicted instances against a ground truth label map
  *   unet_measure_instances / unet_select_instances   per-instance shape, contact and intensity
  *                        tables of a label map; dropping and renumbering of instances
+ *   unet_link_instances  track ids, lineage table and relabelled stack of a sequence of label
+ *                        maps (time lapse or z-stack) by mutually best IoU partners
  *   unet_two_nearest_instances / unet_border_weights / unet_boundary_targets   training targets
  *                        for touching cells from a ground-truth instance map; unet_softmax_loss_*_pw
  *                        take the weight map as per-pixel weights of the cross-entropy
@@ -865,6 +867,58 @@ int unet_measure_instances(const int32_t* labels, const void* image /* nullable 
 int unet_select_instances(const int32_t* labels, const uint8_t* keep /* [N][M] */, int N, int H, int W, int M,
                           int32_t* labels_out /* [N][H][W] */, int32_t* counts /* [N] */,
                           int32_t* new_ids /* [N][M] */, hipStream_t stream);
+
+/* ---- linking instances across the frames of a sequence: tracks and z-stacks (no
+ * reference counterpart) ----
+ * labels is an int32 label map [B][T][H][W]: B independent sequences of T frames
+ * (time points, or the slices of a z-stack), T in 1..65535, H, W <=
+ * UNET_DISTANCE_MAX_DIM and H W <= UNET_GEODESIC_MAX_HW.  Within a frame 0 is
+ * background and the instances carry ids 1..max_instances (in 1..65535; not
+ * necessarily compact, and without meaning across frames).  With IoU threshold
+ * iou_num / iou_den (0 <= iou_num < iou_den), instance b of frame t >= 1 (area A_b)
+ * and its partner a of highest IoU in frame t - 1 as unet_match_instances(gt = frame
+ * t - 1, pred = frame t) defines it (intersection I, area A_a):
+ *   b continues the track of a iff a exists, the best partner of a in frame t is b,
+ *     and I iou_den > iou_num (A_a + A_b - I), i.e. IoU strictly above the threshold;
+ *   otherwise b starts a track, whose parent is the track of a iff a exists and
+ *     2 I > A_b, else 0.
+ * Every instance of frame 0 starts a track with parent 0.  There is no gap closing.
+ * Tracks are numbered 1..n_tracks in the order (first frame, original id).
+ *   tracks int32 [B][T][H][W] (not labels itself): the track id of every pixel with
+ *     a value in 1..max_instances, 0 for every other value.
+ *   table int64 [B][max_tracks][UNET_LINK_COLS], row track - 1: first, last (frame
+ *     indices), parent (a track id or 0), volume (the sum of the areas over the
+ *     frames).  Rows of absent tracks are zero; tracks above max_tracks have no row.
+ *   status int64 [B][UNET_LINK_STATUS]: n_tracks (the true count, also above
+ *     max_tracks; tracks carries the true ids), n_links (instances that continue a
+ *     track), dropped and out_of_range (those of unet_match_instances summed over the
+ *     T - 1 frame pairs of the sequence, so a pixel of an inner frame counts twice;
+ *     T == 1 matches frame 0 against itself and reports that call's).  When dropped or
+ *     out_of_range is nonzero only status is specified.
+ * T min(max_instances, H W) must not exceed 2^31 - 1 (track ids are int32).
+ * Integer arithmetic throughout; every output is bit-reproducible.  labels is only read.
+ * workspace: at least unet_link_workspace_bytes(...) bytes of device memory (the
+ * match tables of every frame pair, one int32 LUT row of max_instances + 1 entries per
+ * frame, one match workspace); it need not be initialised and holds nothing between
+ * calls.  table and status need not be initialised either.  Every bad argument (a
+ * null buffer, tracks == labels, sizes, caps, max_tracks < 1, the threshold, a short
+ * or null workspace) is an error with nothing launched.  All launches are ordinary
+ * kernels on the stream.
+ * UNET_LINK_BLOCK: the ids of a frame are resolved in chunks of this many;
+ * UNET_LINK_LDS_IDS: up to this max_instances the relabelling pass keeps a frame's LUT
+ * row in LDS, above it the row is read through L2. */
+#define UNET_LINK_COLS 4        /* first, last, parent, volume */
+#define UNET_LINK_STATUS 4      /* n_tracks, n_links, dropped, out_of_range */
+#define UNET_LINK_BLOCK 1024
+#define UNET_LINK_LDS_IDS 8191
+/* host only; 0 (with unet_last_error) for a bad argument */
+int64_t unet_link_workspace_bytes(int B, int T, int max_instances, int max_pairs);
+int unet_link_instances(const int32_t* labels, int B, int T, int H, int W,
+                        int max_instances, int max_pairs, int max_tracks, int iou_num, int iou_den,
+                        int32_t* tracks_out,  /* [B][T][H][W] */
+                        int64_t* table,       /* [B][max_tracks][4] row track - 1 */
+                        int64_t* status,      /* [B][4] */
+                        void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
 #ifdef __cplusplus
 }
